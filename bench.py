@@ -3,11 +3,23 @@
 (BASELINE.json configs[1]; configs[2] when launched on 8 GPUs).  One "step" = one full optimizer step of the hot path:
 forward + per-pixel softmax-CE + backward + (gradient all-reduce) + Keras-Adam, dropout active, inputs resident in HBM.
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed steps (all on the product's two-stream
+schedule, no events inside them), the optional `--dump-outputs`, the line -- `metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (milliseconds per timed step).  `--dump-outputs DIR` writes what the LAST timed step computed as DIR/<name>.npy (float32):
+`loss` ([loss, correctly classified pixels], what train_step returns and the metric objects receive), `softmax` (the [N,H,W,K] class
+probabilities of that step's forward pass), `theta` and `grad` (the flat parameter buffer after the step's Adam update and the flat
+gradient buffer it consumed).  An array of more than 4 Mi elements is written as a fixed, seeded sample of 4 Mi of its elements (the
+same elements in every run), so a dump is at most 48 MB.  Parameters, inputs and dropout masks are seeded: two runs with the same arguments
+see identical inputs.
+
+Everything below is measured only with `--full` (`--no-cpu-baseline`, `--no-kernel-events`, `--no-extra` trim a full run): the kernel
+events on sampled steps (`roofline`, `kernels`), the CPU baseline, the other configurations.
 
 `roofline` is for the dominant kernel = the 3x3-conv kernel family with the most ms per step (forward, data gradient or
 weight gradient).  Durations are HIP events recorded on the launch stream, live inside the timed region, on every 8th
@@ -243,8 +255,9 @@ def self_launch(n):
 
 
 def run_workload(model, dev, world, rank, size, channels, classes, batch, dtype, steps, warmup, no_overlap, kernel_events,
-                 sample_every, barrier, fp32_matrix="bf16x6", max_workgroups=None, bucket_mb=25.0):
-    """W warm-up + K timed optimizer steps of one workload -> dict with dt, per-family kernel figures, final loss."""
+                 sample_every, barrier, fp32_matrix="bf16x6", max_workgroups=None, bucket_mb=25.0, dump_dir=None):
+    """W warm-up + K timed optimizer steps of one workload -> dict with dt, per-family kernel figures, final loss.  `dump_dir`: write
+    what the last timed step computed there (dump_outputs), after the clock has stopped."""
     import torch
     G = batch * world
     net = model.UNet(classes, G, channels, learning_rate=3e-4, device=dev, seed=0,
@@ -289,6 +302,8 @@ def run_workload(model, dev, world, rank, size, channels, classes, batch, dtype,
     dt = time.perf_counter() - t0
     net.engine.profile = None
     final_loss = float(net.engine.loss_buf[0].item())
+    if dump_dir:
+        dump_outputs(net, dump_dir)
     kernels = {}
     if prof:
         for key, evs in prof.items():
@@ -320,6 +335,32 @@ def run_workload(model, dev, world, rank, size, channels, classes, batch, dtype,
     del net
     torch.cuda.empty_cache()
     return {"dt": dt, "kernels": kernels, "final_loss": final_loss, "sampled_steps": sampled, "G": G, "buckets": buckets}
+
+
+DUMP_MAX_ELEMS = 4 * 1024 * 1024     # per array: 16 MB of float32; four arrays -> at most 48 MB per dump
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_sample(a, max_elems=DUMP_MAX_ELEMS):
+    """`a` itself up to max_elems elements; beyond, the elements at max_elems seeded positions (ascending, drawn with replacement) of its
+    flattened form -- the same positions for every array of that size."""
+    import numpy as np
+    if a.size <= max_elems:
+        return a
+    idx = np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, a.size, max_elems)
+    return a.reshape(-1)[np.sort(idx)]
+
+
+def dump_outputs(net, dump_dir):
+    """<dump_dir>/{loss,softmax,theta,grad}.npy, float32: what the caller of the last train step holds afterwards."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    os.makedirs(dump_dir, exist_ok=True)
+    e = net.engine
+    for name, t in (("loss", e.loss_buf), ("softmax", e.bufs["softmax"]), ("theta", e.theta), ("grad", e.grad)):
+        a = dump_sample(t.detach().float().cpu().numpy())
+        np.save(os.path.join(dump_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def baseline_config_id(args, world):
@@ -446,10 +487,15 @@ def main():
                          "profiles/r04_overlap_standin.txt is why)")
     ap.add_argument("--bucket-mb", type=float, default=25.0,
                     help="N > 1: size of the gradient all-reduce buckets (default 25; 1000 = one all-reduce behind the whole backward pass, no overlap)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-events", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; see the module docstring)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: kernel events on sampled steps (roofline, kernels), the CPU "
+                         "baseline, the config-4 / config-5 / other-fp32-route runs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full without the kernel events")
     ap.add_argument("--no-overlap", action="store_true", help="run weight gradients on the main stream in every step (A/B switch)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the short config-4 / config-5 runs")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the short config-4 / config-5 runs")
     ap.add_argument("--sample-every", type=int, default=8, help="kernel events on one timed step in this many")
     args = ap.parse_args()
     if args.cpu_baseline_only:
@@ -489,7 +535,8 @@ def main():
     model = importlib.import_module(PKG + ".model")
     sample_every = max(2, min(args.sample_every, args.steps)) if args.steps > 1 else 1
     res = run_workload(model, dev, world, rank, args.size, args.channels, args.classes, args.batch, args.dtype, args.steps,
-                       args.warmup, args.no_overlap, not args.no_kernel_events, sample_every, barrier, args.fp32_matrix, args.max_workgroups, args.bucket_mb)
+                       args.warmup, args.no_overlap, args.full and not args.no_kernel_events, sample_every, barrier, args.fp32_matrix,
+                       args.max_workgroups, args.bucket_mb, dump_dir=args.dump_outputs if rank == 0 else None)
     dt = res["dt"]
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -513,7 +560,7 @@ def main():
         }
 
     extras = []
-    if world == 1 and not args.no_extra and (args.size, args.channels, args.classes, args.batch, args.dtype) == (512, 1, 2, 8, "f32"):
+    if args.full and world == 1 and not args.no_extra and (args.size, args.channels, args.classes, args.batch, args.dtype) == (512, 1, 2, 8, "f32"):
         other = "native" if args.fp32_matrix == "bf16x6" else "bf16x6"
         for (size, ch, kc, b, dty, label, fm, cid) in (
                 (512, 3, 4, 8, "bf16", "BASELINE config 4 per-GPU workload", args.fp32_matrix, "4"),
@@ -562,7 +609,7 @@ def main():
                                   "gradient_allreduce": res["buckets"]}
         if rehearsal:
             out["rehearsal"] = "all %d ranks share GPU 0, collectives over gloo: exercises the N>1 path, not a scaling measurement" % world
-        out["cpu_baseline"] = cpu_baseline_bounded(args) if (world == 1 and not args.no_cpu_baseline) else None
+        out["cpu_baseline"] = cpu_baseline_bounded(args) if (args.full and world == 1 and not args.no_cpu_baseline) else None
         if extras:
             out["extra_configs"] = extras
         out["summary"] = compact
