@@ -164,6 +164,14 @@ int unet_conv1x1_dgrad(const float* dz, int lddz, const float* w, void* dx, int 
 size_t unet_conv1x1_wgrad_workspace(long P, int Cin, int Cout);
 int unet_conv1x1_wgrad(const void* xin, int ldx, int x_bf16, const float* dz, int lddz, float* dw,
                        long P, int Cin, int Cout, void* ws, size_t ws_bytes, void* stream);
+/* The class map reading the last decoder layer's conv output r (fp32) through that layer's BatchNorm coefficients, UNet/model.py:36 then
+ * :136 (forward) and the kernel gradient of :136 under the tape of :216-219: the operand is scale[c] * r + shift[c], formed on load by the
+ * function unet_bn_apply stores y with, so both calls are bit-identical to unet_bn_apply + unet_conv1x1_fwd / unet_conv1x1_wgrad without
+ * the BatchNorm output in memory.  scale / shift: [Cin], 16-byte aligned.  Workspace of the gradient: unet_conv1x1_wgrad_workspace. */
+int unet_conv1x1_fwd_bn(const float* r, int ldr, const float* scale, const float* shift, const float* w, const float* bias,
+                        float* out, int ldo, long P, int Cin, int Cout, int relu, void* stream);
+int unet_conv1x1_wgrad_bn(const float* r, int ldr, const float* scale, const float* shift, const float* dz, int lddz, float* dw,
+                          long P, int Cin, int Cout, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- Conv2DTranspose(2x2, stride 2) of UNet._deconv_layer, UNet/model.py:39-46 (:116,121,126,131) ---------------- */
 /* N,H,W = INPUT dims of the layer; output is [N,2H,2W,Cout].  Needs Cin % 64 == 0 and Cout % 64 == 0. */
@@ -274,6 +282,16 @@ int unet_bn_bwd_any(const void* dy, int lddy, const void* pooled_dy, int ldp, co
                     const void* r, int ldr, const float* gamma, const float* mean, const float* invstd, int C, int relu,
                     void* dz, int lddz, int dz_bf16, float* dgamma, float* dbeta, float* dbias, const float* part_sums, int rows,
                     void* ws, size_t ws_bytes, void* stream, int r_bf16, int dy_bf16, int pooled_dy_bf16, int* host_bias_rows);
+/* unet_bn_bwd_any, plain form with every tensor fp32, for the layer whose BatchNorm output feeds only the class map (UNet/model.py:36 of the
+ * last decoder layer under the tape of :216-219, its dy being the input gradient of :136): takes the class map's own BatchNorm-backward
+ * output dz_logits [N*H*W][lddzl] and kernel w [C][K], 1 <= K <= 8, in place of dy and forms dy[p][c] = sum_k w[c][k] * dz_logits[p][k] on
+ * load with the function unet_conv1x1_dgrad stores it with; grids and the order of every sum are those of unet_bn_bwd_any, so dz, dgamma,
+ * dbeta and the bias partials are bit-identical to unet_conv1x1_dgrad + unet_bn_bwd_any without dy in memory.  Needs C % 8 == 0 and
+ * 16-byte aligned r / dz / per-channel vectors; dbias / host_bias_rows / ws as unet_bn_bwd_any. */
+int unet_bn_bwd_classmap(const float* dz_logits, int lddzl, const float* w, int K, int N, int H, int W,
+                         const float* r, int ldr, const float* gamma, const float* mean, const float* invstd, int C, int relu,
+                         float* dz, int lddz, float* dgamma, float* dbeta, float* dbias, void* ws, size_t ws_bytes, void* stream,
+                         int* host_bias_rows);
 int unet_bn_bwd_bias(const void* ws, int rows, int C, float* dbias, void* stream);
 /* BatchNorm apply (+ the 2x2 max pool when pooled / idx are given) with the conv output it reads (r_bf16) and / or what it writes
  * (y_bf16: y and pooled) stored as bf16 */

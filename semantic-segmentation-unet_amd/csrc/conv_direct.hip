@@ -5,6 +5,7 @@
 // Thread mapping everywhere: consecutive lanes own consecutive channel quads (float4) of one pixel so global
 // accesses are whole 64..256-B pixel rows.
 #include "common.h"
+#include "ends_inline.h"
 
 namespace {
 
@@ -301,7 +302,7 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restri
 template <int X16>
 __global__ __launch_bounds__(256) void conv1x1_narrow_fwd_kernel(const float* __restrict__ x, int ldx,
         const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ out, int ldo,
-        long P, int Cin, int K, int relu) {
+        long P, int Cin, int K, int relu, const float* __restrict__ scale, const float* __restrict__ shift) {
     extern __shared__ __attribute__((aligned(16))) float sW[];        // [Cin][K]
     for (int i = threadIdx.x; i < Cin * K; i += 256) sW[i] = w[i];
     __syncthreads();
@@ -323,6 +324,12 @@ __global__ __launch_bounds__(256) void conv1x1_narrow_fwd_kernel(const float* __
                 for (int u = 0; u < PU; ++u) {
                     const long pix = base + u < P ? base + u : P - 1;
                     xv[u] = ld_quad<X16>(x, (size_t)pix * ldx + 4 * cq);
+                }
+                if (scale) {                                          // x is the producer's conv output: BatchNorm apply on load
+#pragma unroll
+                    for (int u = 0; u < PU; ++u)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) xv[u][e] = unet_bn_y(scale[4 * cq + e], xv[u][e], shift[4 * cq + e]);
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
@@ -382,13 +389,9 @@ __global__ __launch_bounds__(256) void conv1x1_narrow_dgrad_kernel(const float* 
             float g[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) g[k] = k < K ? dz[(size_t)pix * lddz + k] : 0.f;
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc;
 #pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (k < K) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[e] += g[k] * wr[e][k];
-                }
+            for (int e = 0; e < 4; ++e) acc[e] = unet_classmap_dy<8>(g, wr[e], K);
             st_quad<DX16>(dx, (size_t)pix * lddx + 4 * cq, acc);
         }
         return;
@@ -399,7 +402,7 @@ __global__ __launch_bounds__(256) void conv1x1_narrow_dgrad_kernel(const float* 
         for (int k = 0; k < K; ++k) {
             const float g = dz[(size_t)pix * lddz + k];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc[e] += g * sW[(4 * cq + e) * K + k];
+            for (int e = 0; e < 4; ++e) acc[e] = unet_classmap_dy_term(acc[e], g, sW[(4 * cq + e) * K + k]);     // (the terms of unet_classmap_dy, K unbounded)
         }
         st_quad<DX16>(dx, (size_t)pix * lddx + 4 * cq, acc);
     }
@@ -408,7 +411,8 @@ __global__ __launch_bounds__(256) void conv1x1_narrow_dgrad_kernel(const float* 
 // wgrad: part[blk][ci][k] = sum over the block's pixels of x[p][ci] * dz[p][k]   (k0..k0+8 per pass)
 template <int X16>
 __global__ __launch_bounds__(256) void conv1x1_narrow_wgrad_kernel(const float* __restrict__ x, int ldx,
-        const float* __restrict__ dz, int lddz, float* __restrict__ part, long P, int Cin, int K, long pix_per_block) {
+        const float* __restrict__ dz, int lddz, float* __restrict__ part, long P, int Cin, int K, long pix_per_block,
+        const float* __restrict__ scale, const float* __restrict__ shift) {
     extern __shared__ __attribute__((aligned(16))) float sR[];        // [npl][4*tpp][8]
     const int nq = Cin >> 2;
     const int tpp = nq < 256 ? nq : 256, npl = 256 / tpp;
@@ -416,6 +420,8 @@ __global__ __launch_bounds__(256) void conv1x1_narrow_wgrad_kernel(const float* 
     const long p0 = (long)blockIdx.x * pix_per_block;
     long p1 = p0 + pix_per_block; if (p1 > P) p1 = P;
     for (int qq = q; qq < nq; qq += tpp) {
+        f32x4 sa = {1.f, 1.f, 1.f, 1.f}, sb = {0.f, 0.f, 0.f, 0.f};   // BatchNorm apply on load (scale given): x is the producer's conv output
+        if (scale) { sa = *reinterpret_cast<const f32x4*>(scale + 4 * qq); sb = *reinterpret_cast<const f32x4*>(shift + 4 * qq); }
         for (int k0 = 0; k0 < K; k0 += 8) {
             float acc[4][8];
 #pragma unroll
@@ -430,6 +436,10 @@ __global__ __launch_bounds__(256) void conv1x1_narrow_wgrad_kernel(const float* 
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     xv[u] = ld_quad<X16>(x, (size_t)(pix + u * (long)npl) * ldx + 4 * qq);
+                    if (scale) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) xv[u][e] = unet_bn_y(sa[e], xv[u][e], sb[e]);
+                    }
 #pragma unroll
                     for (int j = 0; j < 8; ++j) g[u][j] = (k0 + j < K) ? dz[(size_t)(pix + u * (long)npl) * lddz + k0 + j] : 0.f;
                 }
@@ -443,7 +453,11 @@ __global__ __launch_bounds__(256) void conv1x1_narrow_wgrad_kernel(const float* 
                         }
             }
             for (; pix < p1; pix += npl) {
-                const f32x4 xv = ld_quad<X16>(x, (size_t)pix * ldx + 4 * qq);
+                f32x4 xv = ld_quad<X16>(x, (size_t)pix * ldx + 4 * qq);
+                if (scale) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) xv[e] = unet_bn_y(sa[e], xv[e], sb[e]);
+                }
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     if (k0 + j < K) {
@@ -504,10 +518,27 @@ __device__ __forceinline__ float cm_sum8(float v) {
     return v;
 }
 
-template <int KK>                     // KK = 4 or 8: accumulators per lane
+// BN: x is the producer's conv output r (fp32) and the operand is unet_bn_y(scale, r, shift) -- what unet_bn_apply would have stored
+template <int BN> __device__ __forceinline__ void cm_coefs(float (&a)[8], float (&b)[8], const float* scale, const float* shift, int c0) {
+    if constexpr (BN != 0) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { a[e] = scale[c0 + e]; b[e] = shift[c0 + e]; }
+    }
+}
+template <int BN> __device__ __forceinline__ void cm_apply8(float (&v)[8], const float (&a)[8], const float (&b)[8]) {
+    if constexpr (BN != 0) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = unet_bn_y(a[e], v[e], b[e]);
+    }
+}
+
+template <int KK, int BN>             // KK = 4 or 8: accumulators per lane
 __global__ __launch_bounds__(256) void classmap64_fwd_kernel(const float* __restrict__ x, int ldx, int x16, const float* __restrict__ w,
-        const float* __restrict__ bias, float* __restrict__ out, int ldo, int P, int K, int relu) {
+        const float* __restrict__ bias, float* __restrict__ out, int ldo, int P, int K, int relu, const float* __restrict__ scale,
+        const float* __restrict__ shift) {
     const int sub = threadIdx.x & 7, pl = threadIdx.x >> 3;
+    float sa[8], sb[8];
+    cm_coefs<BN>(sa, sb, scale, shift, 8 * sub);
     float wr[8][KK];
 #pragma unroll
     for (int e = 0; e < 8; ++e)
@@ -522,6 +553,7 @@ __global__ __launch_bounds__(256) void classmap64_fwd_kernel(const float* __rest
         for (int u = 0; u < U; ++u) { const int pix = pix0 + u * stride < P ? pix0 + u * stride : pix0; cm_load8(x, (size_t)pix * ldx + 8 * sub, x16, xv[u]); }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
+            cm_apply8<BN>(xv[u], sa, sb);
             float mine = 0.f;
 #pragma unroll
             for (int k = 0; k < KK; ++k) {
@@ -562,11 +594,7 @@ __global__ __launch_bounds__(256) void classmap64_dgrad_kernel(const float* __re
             if (pix >= P) break;
             float acc[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                acc[e] = 0.f;
-#pragma unroll
-                for (int k = 0; k < KK; ++k) acc[e] = fmaf(g[u][k], wr[e][k], acc[e]);
-            }
+            for (int e = 0; e < 8; ++e) acc[e] = unet_classmap_dy<KK>(g[u], wr[e], KK);
             const size_t o = (size_t)pix * lddx + 8 * sub;
             if (dx16) {
                 uint4 h;
@@ -585,11 +613,13 @@ __global__ __launch_bounds__(256) void classmap64_dgrad_kernel(const float* __re
 
 // part[blk][ci][k] = sum over the block's pixels of x[p][ci] * dz[p][k]: per-lane sums, then the 8 pixel lanes of a wave (xor shuffles), then the
 // 4 waves through LDS, all in a fixed order
-template <int KK>
+template <int KK, int BN>
 __global__ __launch_bounds__(256) void classmap64_wgrad_kernel(const float* __restrict__ x, int ldx, int x16, const float* __restrict__ dz, int lddz,
-        float* __restrict__ part, int P, int K, int pix_per_block) {
+        float* __restrict__ part, int P, int K, int pix_per_block, const float* __restrict__ scale, const float* __restrict__ shift) {
     __shared__ float sR[4][64][KK];
     const int sub = threadIdx.x & 7, pl = threadIdx.x >> 3, wv = threadIdx.x >> 6;
+    float sa[8], sb[8];
+    cm_coefs<BN>(sa, sb, scale, shift, 8 * sub);
     const bool vec4 = K == 4 && lddz == 4;
     const int p0 = (int)blockIdx.x * pix_per_block;
     const int p1 = p0 + pix_per_block < P ? p0 + pix_per_block : P;
@@ -610,6 +640,7 @@ __global__ __launch_bounds__(256) void classmap64_wgrad_kernel(const float* __re
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (pix0 + u * 32 >= p1) break;
+            cm_apply8<BN>(xv[u], sa, sb);
 #pragma unroll
             for (int e = 0; e < 8; ++e)
 #pragma unroll
@@ -1011,20 +1042,41 @@ extern "C" int unet_conv3x3_wgrad_direct(const float* xin, int ldx, const void* 
 }
 
 // x_bf16 / dx_bf16 below: the 64-channel side of the class-map layer is stored as bf16 (leading dimension in elements); arithmetic fp32
-extern "C" int unet_conv1x1_fwd(const void* x, int ldx, int x_bf16, const float* w, const float* bias, float* out, int ldo,
-                                long P, int Cin, int Cout, int relu, void* stream) {
+// scale / shift (both or neither; fp32 x only): BatchNorm apply on load, x is the producer layer's conv output
+static int conv1x1_fwd_launch(const void* x, int ldx, int x_bf16, const float* scale, const float* shift, const float* w, const float* bias,
+                              float* out, int ldo, long P, int Cin, int Cout, int relu, void* stream) {
     UNET_CHECK_ARG(x && w && out && P > 0 && Cin > 0 && Cout > 0 && Cin % 4 == 0 && ldx % 4 == 0 && ldx >= Cin && ldo >= Cout);
     UNET_CHECK_ARG(unet_aligned16(x) && (size_t)Cin * Cout * 4 <= 64 * 1024);
+    UNET_CHECK_ARG((scale == nullptr) == (shift == nullptr) && !(scale && x_bf16));
+    hipStream_t st = (hipStream_t)stream;
     if (Cin == 64 && Cout <= 8 && ldx % 8 == 0 && P < (1L << 31)) {            // the network's class map
         const int b8 = classmap64_blocks(P);
-        if (Cout <= 4) classmap64_fwd_kernel<4><<<b8, 256, 0, (hipStream_t)stream>>>((const float*)x, ldx, x_bf16, w, bias, out, ldo, (int)P, Cout, relu);
-        else           classmap64_fwd_kernel<8><<<b8, 256, 0, (hipStream_t)stream>>>((const float*)x, ldx, x_bf16, w, bias, out, ldo, (int)P, Cout, relu);
+        if (scale) {
+            if (Cout <= 4) classmap64_fwd_kernel<4, 1><<<b8, 256, 0, st>>>((const float*)x, ldx, 0, w, bias, out, ldo, (int)P, Cout, relu, scale, shift);
+            else           classmap64_fwd_kernel<8, 1><<<b8, 256, 0, st>>>((const float*)x, ldx, 0, w, bias, out, ldo, (int)P, Cout, relu, scale, shift);
+        } else {
+            if (Cout <= 4) classmap64_fwd_kernel<4, 0><<<b8, 256, 0, st>>>((const float*)x, ldx, x_bf16, w, bias, out, ldo, (int)P, Cout, relu, nullptr, nullptr);
+            else           classmap64_fwd_kernel<8, 0><<<b8, 256, 0, st>>>((const float*)x, ldx, x_bf16, w, bias, out, ldo, (int)P, Cout, relu, nullptr, nullptr);
+        }
         return UNET_LAUNCH_STATUS();
     }
     long blocks = (P + 63) / 64; if (blocks > 4096) blocks = 4096;
-    if (x_bf16) conv1x1_narrow_fwd_kernel<1><<<(int)blocks, 256, (size_t)Cin * Cout * 4, (hipStream_t)stream>>>((const float*)x, ldx, w, bias, out, ldo, P, Cin, Cout, relu);
-    else        conv1x1_narrow_fwd_kernel<0><<<(int)blocks, 256, (size_t)Cin * Cout * 4, (hipStream_t)stream>>>((const float*)x, ldx, w, bias, out, ldo, P, Cin, Cout, relu);
+    if (x_bf16) conv1x1_narrow_fwd_kernel<1><<<(int)blocks, 256, (size_t)Cin * Cout * 4, st>>>((const float*)x, ldx, w, bias, out, ldo, P, Cin, Cout, relu, nullptr, nullptr);
+    else        conv1x1_narrow_fwd_kernel<0><<<(int)blocks, 256, (size_t)Cin * Cout * 4, st>>>((const float*)x, ldx, w, bias, out, ldo, P, Cin, Cout, relu, scale, shift);
     return UNET_LAUNCH_STATUS();
+}
+
+extern "C" int unet_conv1x1_fwd(const void* x, int ldx, int x_bf16, const float* w, const float* bias, float* out, int ldo,
+                                long P, int Cin, int Cout, int relu, void* stream) {
+    return conv1x1_fwd_launch(x, ldx, x_bf16, nullptr, nullptr, w, bias, out, ldo, P, Cin, Cout, relu, stream);
+}
+
+// unet_bn_apply + unet_conv1x1_fwd without the BatchNorm output in memory: r [P][ldr] is the producer layer's fp32 conv output, the operand
+// is scale[c] * r + shift[c] formed on load by the function unet_bn_apply stores with -- bit-identical to the two calls
+extern "C" int unet_conv1x1_fwd_bn(const float* r, int ldr, const float* scale, const float* shift, const float* w, const float* bias,
+                                   float* out, int ldo, long P, int Cin, int Cout, int relu, void* stream) {
+    UNET_CHECK_ARG(scale && shift && unet_aligned16(scale) && unet_aligned16(shift));
+    return conv1x1_fwd_launch(r, ldr, 0, scale, shift, w, bias, out, ldo, P, Cin, Cout, relu, stream);
 }
 
 extern "C" int unet_conv1x1_dgrad(const float* dz, int lddz, const float* w, void* dx, int lddx, int dx_bf16,
@@ -1049,26 +1101,45 @@ extern "C" size_t unet_conv1x1_wgrad_workspace(long P, int Cin, int Cout) {
     return (size_t)direct_wgrad_blocks(P) * Cin * Cout * sizeof(float);
 }
 
-extern "C" int unet_conv1x1_wgrad(const void* xin, int ldx, int x_bf16, const float* dz, int lddz, float* dw,
-                                  long P, int Cin, int Cout, void* ws, size_t ws_bytes, void* stream) {
+static int conv1x1_wgrad_launch(const void* xin, int ldx, int x_bf16, const float* scale, const float* shift, const float* dz, int lddz, float* dw,
+                                long P, int Cin, int Cout, void* ws, size_t ws_bytes, void* stream) {
     UNET_CHECK_ARG(xin && dz && dw && ws && P > 0 && Cin > 0 && Cout > 0 && Cin % 4 == 0 && ldx % 4 == 0);
+    UNET_CHECK_ARG((scale == nullptr) == (shift == nullptr) && !(scale && x_bf16));
     const int nq = Cin / 4, tpp = nq < 256 ? nq : 256;
     UNET_CHECK_ARG(256 % tpp == 0 && nq % tpp == 0 && unet_aligned16(xin));
     const int blocks = direct_wgrad_blocks(P);
     if (ws_bytes < unet_conv1x1_wgrad_workspace(P, Cin, Cout)) return UNET_ENOSPC;
     const long ppb = (P + blocks - 1) / blocks;
     const size_t smem = (size_t)(256 / tpp) * 4 * tpp * 8 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
     if (Cin == 64 && Cout <= 8 && ldx % 8 == 0 && P < (1L << 31) && (Cout != 4 || lddz != 4 || unet_aligned16(dz))) {
-        if (Cout <= 4) classmap64_wgrad_kernel<4><<<blocks, 256, 0, (hipStream_t)stream>>>((const float*)xin, ldx, x_bf16, dz, lddz, (float*)ws, (int)P, Cout, (int)ppb);
-        else           classmap64_wgrad_kernel<8><<<blocks, 256, 0, (hipStream_t)stream>>>((const float*)xin, ldx, x_bf16, dz, lddz, (float*)ws, (int)P, Cout, (int)ppb);
+        if (scale) {
+            if (Cout <= 4) classmap64_wgrad_kernel<4, 1><<<blocks, 256, 0, st>>>((const float*)xin, ldx, 0, dz, lddz, (float*)ws, (int)P, Cout, (int)ppb, scale, shift);
+            else           classmap64_wgrad_kernel<8, 1><<<blocks, 256, 0, st>>>((const float*)xin, ldx, 0, dz, lddz, (float*)ws, (int)P, Cout, (int)ppb, scale, shift);
+        } else {
+            if (Cout <= 4) classmap64_wgrad_kernel<4, 0><<<blocks, 256, 0, st>>>((const float*)xin, ldx, x_bf16, dz, lddz, (float*)ws, (int)P, Cout, (int)ppb, nullptr, nullptr);
+            else           classmap64_wgrad_kernel<8, 0><<<blocks, 256, 0, st>>>((const float*)xin, ldx, x_bf16, dz, lddz, (float*)ws, (int)P, Cout, (int)ppb, nullptr, nullptr);
+        }
         int rc2 = UNET_LAUNCH_STATUS(); if (rc2) return rc2;
-        sum_partials_kernel<<<unet_cdiv((long)Cin * Cout, 4), 256, 0, (hipStream_t)stream>>>((const float*)ws, dw, (long)Cin * Cout, blocks);
+        sum_partials_kernel<<<unet_cdiv((long)Cin * Cout, 4), 256, 0, st>>>((const float*)ws, dw, (long)Cin * Cout, blocks);
         return UNET_LAUNCH_STATUS();
     }
-    if (x_bf16) conv1x1_narrow_wgrad_kernel<1><<<blocks, 256, smem, (hipStream_t)stream>>>((const float*)xin, ldx, dz, lddz, (float*)ws, P, Cin, Cout, ppb);
-    else        conv1x1_narrow_wgrad_kernel<0><<<blocks, 256, smem, (hipStream_t)stream>>>((const float*)xin, ldx, dz, lddz, (float*)ws, P, Cin, Cout, ppb);
+    if (x_bf16) conv1x1_narrow_wgrad_kernel<1><<<blocks, 256, smem, st>>>((const float*)xin, ldx, dz, lddz, (float*)ws, P, Cin, Cout, ppb, nullptr, nullptr);
+    else        conv1x1_narrow_wgrad_kernel<0><<<blocks, 256, smem, st>>>((const float*)xin, ldx, dz, lddz, (float*)ws, P, Cin, Cout, ppb, scale, shift);
     int rc = UNET_LAUNCH_STATUS(); if (rc) return rc;
     const long n = (long)Cin * Cout;
-    sum_partials_kernel<<<unet_cdiv(n, 4), 256, 0, (hipStream_t)stream>>>((const float*)ws, dw, n, blocks);
+    sum_partials_kernel<<<unet_cdiv(n, 4), 256, 0, st>>>((const float*)ws, dw, n, blocks);
     return UNET_LAUNCH_STATUS();
+}
+
+extern "C" int unet_conv1x1_wgrad(const void* xin, int ldx, int x_bf16, const float* dz, int lddz, float* dw,
+                                  long P, int Cin, int Cout, void* ws, size_t ws_bytes, void* stream) {
+    return conv1x1_wgrad_launch(xin, ldx, x_bf16, nullptr, nullptr, dz, lddz, dw, P, Cin, Cout, ws, ws_bytes, stream);
+}
+
+// unet_bn_apply + unet_conv1x1_wgrad without the BatchNorm output in memory (see unet_conv1x1_fwd_bn); workspace: unet_conv1x1_wgrad_workspace
+extern "C" int unet_conv1x1_wgrad_bn(const float* r, int ldr, const float* scale, const float* shift, const float* dz, int lddz, float* dw,
+                                     long P, int Cin, int Cout, void* ws, size_t ws_bytes, void* stream) {
+    UNET_CHECK_ARG(scale && shift && unet_aligned16(scale) && unet_aligned16(shift));
+    return conv1x1_wgrad_launch(r, ldr, 0, scale, shift, dz, lddz, dw, P, Cin, Cout, ws, ws_bytes, stream);
 }

@@ -7,6 +7,7 @@
 // class-map tensors), 256/tpp pixels in flight per block.  Per-channel sums are accumulated in fp64 per lane,
 // combined through LDS, written as per-block partials and summed in a fixed order (bit-stable run to run).
 #include "common.h"
+#include "ends_inline.h"
 #include <stdlib.h>
 
 namespace {
@@ -327,7 +328,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) v[u][e] = fmaf(a[e], v[u][e], b[e]);
+            for (int e = 0; e < VEC; ++e) v[u][e] = unet_bn_y(a[e], v[u][e], b[e]);
             vstore_dt<VEC>(y, (size_t)(pix + u * S) * ldy + l.c0, v[u], out16 & 1);
         }
     }
@@ -335,7 +336,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
         float v[VEC];
         vload_dt<VEC, kApplyNT>(v, r, (size_t)pix * ldr + l.c0, out16 & 2);
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) v[e] = fmaf(a[e], v[e], b[e]);
+        for (int e = 0; e < VEC; ++e) v[e] = unet_bn_y(a[e], v[e], b[e]);
         vstore_dt<VEC>(y, (size_t)pix * ldy + l.c0, v, out16 & 1);
     }
 }
@@ -351,7 +352,7 @@ __global__ __launch_bounds__(256) void bn_apply_flat_kernel(const float* __restr
         float v[VEC], a[VEC], b[VEC];
         vload_dt<VEC>(v, r, (size_t)pix * ldr + c0, out16 & 2); vload<VEC>(a, scale + c0); vload<VEC>(b, shift + c0);
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) v[e] = fmaf(a[e], v[e], b[e]);
+        for (int e = 0; e < VEC; ++e) v[e] = unet_bn_y(a[e], v[e], b[e]);
         vstore_dt<VEC>(y, (size_t)pix * ldy + c0, v, out16 & 1);
     }
 }
@@ -477,10 +478,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
             vload<VEC>(dg, dgamma + l.c0); vload<VEC>(db, dbeta + l.c0);
             const float invP = 1.0f / (float)P;
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                const float a = ga[e] * is[e], c1 = db[e] * invP, c2 = dg[e] * invP;
-                A[e] = a; Bc[e] = -(a * (c2 * is[e])); K[e] = a * (c2 * is[e] * mu[e] - c1);
-            }
+            for (int e = 0; e < VEC; ++e) unet_bn_bwd_coef(ga[e], is[e], mu[e], dg[e], db[e], invP, A[e], Bc[e], K[e]);
         }
         long pix = p0 + l.pl;
         const long st = l.npl;
@@ -499,8 +497,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                 float o[VEC];
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
-                    float d = fmaf(A[e], g[u][e], fmaf(Bc[e], v[u][e], K[e]));
-                    if (relu && !(v[u][e] > 0.f)) d = 0.f;
+                    const float d = unet_bn_bwd_dz(A[e], Bc[e], K[e], g[u][e], v[u][e], relu);
                     o[e] = d; sum4[e] += d;
                 }
                 vstore_dt<VEC>(dz, (size_t)(pix + u * st) * lddz + l.c0, o, dt & 1);
@@ -514,11 +511,145 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
             add_pool_grad<VEC>(g, pg, pix, l.c0);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
-                float d = fmaf(A[e], g[e], fmaf(Bc[e], v[e], K[e]));
-                if (relu && !(v[e] > 0.f)) d = 0.f;
+                const float d = unet_bn_bwd_dz(A[e], Bc[e], K[e], g[e], v[e], relu);
                 o[e] = d; acc[0][e] += (double)d;
             }
             vstore_dt<VEC>(dz, (size_t)pix * lddz + l.c0, o, dt & 1);
+        }
+    }
+    block_combine<VEC, 1>(acc, l, C, part, gridDim.x, sRd);
+}
+
+// ---- BatchNorm backward of the layer in front of the class map, dy formed on load -----------------------------------------------------
+// That layer's dy is the class map's input gradient dy[p][c] = sum_k w[c][k] * dzl[p][k] (K <= 8 classes): K multiply-adds from a tensor
+// 32 / K times smaller than dy.  The two passes below are bn_bwd_reduce_kernel<8> / bn_bwd_apply_kernel<8> (plain form, fp32 tensors) with
+// the dy load replaced by unet_classmap_dy -- the function the class-map data-gradient kernels store dy with -- on the same lane layout,
+// grid and block ranges, so every sum is added in the same order and dz / dgamma / dbeta / the bias partials are bit-identical to
+// unet_conv1x1_dgrad + unet_bn_bwd_any, without the write and the two reads of dy.  A lane keeps the 8 x K weights of its channel octet
+// in registers; the K class gradients of a pixel are one load that the lanes of the pixel share.
+template <int KK> __device__ __forceinline__ void cmdy_weights(float (&wr)[8][KK], const float* w, int c0, int K) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+#pragma unroll
+        for (int k = 0; k < KK; ++k) wr[e][k] = k < K ? w[(size_t)(c0 + e) * K + k] : 0.f;
+}
+// vk: the class-map tensor is dense (leading dimension K) and K is 2 or 4 -- one 8- / 16-byte load per pixel
+template <int KK> __device__ __forceinline__ void cmdy_loadk(float (&g)[KK], const float* dzl, size_t elem, int K, bool vk) {
+    if (vk && K == 2) {
+        const f32x2 a = *reinterpret_cast<const f32x2*>(dzl + elem);
+#pragma unroll
+        for (int k = 0; k < KK; ++k) g[k] = k < 2 ? a[k & 1] : 0.f;
+    } else if (vk) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(dzl + elem);
+#pragma unroll
+        for (int k = 0; k < KK; ++k) g[k] = k < 4 ? a[k & 3] : 0.f;
+    } else {
+#pragma unroll
+        for (int k = 0; k < KK; ++k) g[k] = k < K ? dzl[elem + k] : 0.f;
+    }
+}
+
+template <int KK>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_classmap_kernel(const float* __restrict__ dzl, int lddzl, const float* __restrict__ w, int K,
+        const float* __restrict__ r, int ldr, const float* __restrict__ mean, long P, int C, int tpp, long ppb, double* __restrict__ part, int vk) {
+    constexpr int VEC = 8;
+    extern __shared__ __attribute__((aligned(16))) double sRd[];
+    const Lay l = make_lay<VEC>(C, tpp);
+    const long p0 = (long)blockIdx.x * ppb; long p1 = p0 + ppb; if (p1 > P) p1 = P;
+    double acc[2][VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) { acc[0][e] = 0.0; acc[1][e] = 0.0; }
+    if (l.active) {
+        float mu[VEC]; vload<VEC>(mu, mean + l.c0);
+        float wr[VEC][KK]; cmdy_weights<KK>(wr, w, l.c0, K);
+        long pix = p0 + l.pl;
+        const long st = l.npl;
+        for (; pix + 3 * st < p1; pix += 4 * st) {
+            float gk[4][KK], v[4][VEC];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                cmdy_loadk<KK>(gk[u], dzl, (size_t)(pix + u * st) * lddzl, K, vk != 0); vload<VEC>(v[u], r + (size_t)(pix + u * st) * ldr + l.c0);
+            }
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                float g[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) g[u] = unet_classmap_dy<KK>(gk[u], wr[e], K);
+                const float s0 = (g[0] + g[1]) + (g[2] + g[3]);
+                float s1 = g[0] * (v[0][e] - mu[e]);
+                s1 = fmaf(g[1], v[1][e] - mu[e], s1); s1 = fmaf(g[2], v[2][e] - mu[e], s1); s1 = fmaf(g[3], v[3][e] - mu[e], s1);
+                acc[0][e] += (double)s0; acc[1][e] += (double)s1;
+            }
+        }
+        for (; pix < p1; pix += st) {
+            float gk[KK], v[VEC];
+            cmdy_loadk<KK>(gk, dzl, (size_t)pix * lddzl, K, vk != 0); vload<VEC>(v, r + (size_t)pix * ldr + l.c0);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const float g = unet_classmap_dy<KK>(gk, wr[e], K);
+                acc[0][e] += (double)g; acc[1][e] += (double)(g * (v[e] - mu[e]));
+            }
+        }
+    }
+    block_combine<VEC, 2>(acc, l, C, part, gridDim.x, sRd);
+}
+
+template <int KK>
+__global__ __launch_bounds__(256) void bn_bwd_apply_classmap_kernel(const float* __restrict__ dzl, int lddzl, const float* __restrict__ w, int K,
+        const float* __restrict__ r, int ldr, const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ invstd,
+        const float* __restrict__ dgamma, const float* __restrict__ dbeta, long P, int C, int tpp, long ppb, int relu,
+        float* __restrict__ dz, int lddz, double* __restrict__ part, int vk) {
+    constexpr int VEC = 8;
+    extern __shared__ __attribute__((aligned(16))) double sRd[];
+    const Lay l = make_lay<VEC>(C, tpp);
+    const long p0 = (long)blockIdx.x * ppb; long p1 = p0 + ppb; if (p1 > P) p1 = P;
+    double acc[1][VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) acc[0][e] = 0.0;
+    if (l.active) {
+        float A[VEC], Bc[VEC], Kc[VEC];
+        {
+            float mu[VEC], is[VEC], ga[VEC], dg[VEC], db[VEC];
+            vload<VEC>(mu, mean + l.c0); vload<VEC>(is, invstd + l.c0); vload<VEC>(ga, gamma + l.c0);
+            vload<VEC>(dg, dgamma + l.c0); vload<VEC>(db, dbeta + l.c0);
+            const float invP = 1.0f / (float)P;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) unet_bn_bwd_coef(ga[e], is[e], mu[e], dg[e], db[e], invP, A[e], Bc[e], Kc[e]);
+        }
+        float wr[VEC][KK]; cmdy_weights<KK>(wr, w, l.c0, K);
+        long pix = p0 + l.pl;
+        const long st = l.npl;
+        for (; pix + 3 * st < p1; pix += 4 * st) {
+            float gk[4][KK], v[4][VEC];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                cmdy_loadk<KK>(gk[u], dzl, (size_t)(pix + u * st) * lddzl, K, vk != 0); vload<VEC>(v[u], r + (size_t)(pix + u * st) * ldr + l.c0);
+            }
+            float sum4[VEC];
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) sum4[e] = 0.f;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                float o[VEC];
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) {
+                    const float d = unet_bn_bwd_dz(A[e], Bc[e], Kc[e], unet_classmap_dy<KK>(gk[u], wr[e], K), v[u][e], relu);
+                    o[e] = d; sum4[e] += d;
+                }
+                vstore<VEC>(dz + (size_t)(pix + u * st) * lddz + l.c0, o);
+            }
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[0][e] += (double)sum4[e];
+        }
+        for (; pix < p1; pix += st) {
+            float gk[KK], v[VEC], o[VEC];
+            cmdy_loadk<KK>(gk, dzl, (size_t)pix * lddzl, K, vk != 0); vload<VEC>(v, r + (size_t)pix * ldr + l.c0);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const float d = unet_bn_bwd_dz(A[e], Bc[e], Kc[e], unet_classmap_dy<KK>(gk, wr[e], K), v[e], relu);
+                o[e] = d; acc[0][e] += (double)d;
+            }
+            vstore<VEC>(dz + (size_t)pix * lddz + l.c0, o);
         }
     }
     block_combine<VEC, 1>(acc, l, C, part, gridDim.x, sRd);
@@ -1022,6 +1153,16 @@ extern "C" int unet_bn_apply_maxpool(const float* r, int ldr, const float* scale
     return launch_bn_apply(r, ldr, 0, scale, shift, y, ldy, 0, pooled, ldp, idx, N, H, W, C, (hipStream_t)stream);
 }
 
+// Block counts of the plain (un-pooled) reduce and apply passes: the plan's count, capped to one resident wave of workgroups of
+// bn_bwd_reduce_kernel / bn_bwd_apply_kernel.  The block ranges they give decide the order of every sum, so every caller that must
+// agree bit for bit with unet_bn_bwd_any (unet_bn_bwd_classmap) takes them from here.
+static void bn_bwd_plain_grids(const Plan& pl, int* nb_r, int* nb_a) {
+    const int cr = pl.vec == 8 ? reduce_grid<8>(pl.smem2) : pl.vec == 4 ? reduce_grid<4>(pl.smem2) : reduce_grid<1>(pl.smem2);
+    const int ca = pl.vec == 8 ? apply_grid<8>(pl.smem1) : pl.vec == 4 ? apply_grid<4>(pl.smem1) : apply_grid<1>(pl.smem1);
+    *nb_r = pl.nblk < cr ? pl.nblk : cr;
+    *nb_a = pl.nblk < ca ? pl.nblk : ca;
+}
+
 static int bn_bwd_launch(const float* dy, int lddy, const float* r, int ldr, const float* gamma, const float* mean,
         const float* invstd, long P, int C, int relu, float* dz, int lddz, float* dgamma, float* dbeta, float* dbias,
         const float* part_sums, int rows, PoolGrad pg, void* ws, size_t ws_bytes, void* stream, int dt = 0, int* host_bias_rows = nullptr) {
@@ -1038,13 +1179,8 @@ static int bn_bwd_launch(const float* dy, int lddy, const float* r, int ldr, con
     int rc;
     if ((dt || pg.p16) && pl.vec < 4) return UNET_EINVAL;
     // grids: the plan's block count, capped to one resident wave of workgroups of the kernel that runs
-    int nb_r = pl.nblk, nb_a = pl.nblk;
-    {
-        const int cr = pl.vec == 8 ? reduce_grid<8>(pl.smem2) : pl.vec == 4 ? reduce_grid<4>(pl.smem2) : reduce_grid<1>(pl.smem2);
-        const int ca = pl.vec == 8 ? apply_grid<8>(pl.smem1) : pl.vec == 4 ? apply_grid<4>(pl.smem1) : apply_grid<1>(pl.smem1);
-        if (nb_r > cr) nb_r = cr;
-        if (nb_a > ca) nb_a = ca;
-    }
+    int nb_r, nb_a;
+    bn_bwd_plain_grids(pl, &nb_r, &nb_a);
     const bool pooled_form = pg.pdy != nullptr && pl.vec >= 4;       // window-per-lane kernels: grids over the POOLED pixels
     const long Pw = pooled_form ? P / 4 : P;
     if (pooled_form) {
@@ -1144,6 +1280,47 @@ extern "C" int unet_bn_bwd_any(const void* dy, int lddy, const void* pooled_dy, 
     const PoolGrad pg = pooled_dy ? PoolGrad{(const float*)pooled_dy, ldp, idx, H, W, C, pooled_dy_bf16 ? 1 : 0} : PoolGrad{nullptr, 0, nullptr, 0, 0, 0, 0};
     return bn_bwd_launch((const float*)dy, lddy, (const float*)r, ldr, gamma, mean, invstd, (long)N * H * W, C, relu, (float*)dz, lddz, dgamma, dbeta, dbias,
                          part_sums, part_sums ? rows : 0, pg, ws, ws_bytes, stream, (dz_bf16 ? 1 : 0) | (r_bf16 ? 2 : 0) | (dy_bf16 ? 4 : 0), host_bias_rows);
+}
+
+// unet_bn_bwd_any (plain form, every tensor fp32) for the layer whose BatchNorm output feeds the class map only: instead of dy it takes
+// the class map's own BatchNorm-backward output dz_logits [P][lddzl] and kernel w [C][K], 1 <= K <= 8, and forms
+// dy[p][c] = sum_k w[c][k] * dz_logits[p][k] on load, as unet_conv1x1_dgrad would have stored it.  Same grids, same order of every sum:
+// dz, dgamma, dbeta and the bias partials are bit-identical to unet_conv1x1_dgrad + unet_bn_bwd_any.  Needs the 8-channels-per-lane layout.
+extern "C" int unet_bn_bwd_classmap(const float* dz_logits, int lddzl, const float* w, int K, int N, int H, int W,
+        const float* r, int ldr, const float* gamma, const float* mean, const float* invstd, int C, int relu,
+        float* dz, int lddz, float* dgamma, float* dbeta, float* dbias, void* ws, size_t ws_bytes, void* stream, int* host_bias_rows) {
+    UNET_CHECK_ARG(dz_logits && w && r && gamma && mean && invstd && dz && dgamma && dbeta && (dbias || host_bias_rows) && ws);
+    UNET_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && K >= 1 && K <= 8 && lddzl >= K && ldr >= C && lddz >= C);
+    const long P = (long)N * H * W;
+    const bool al = unet_aligned16(r) && unet_aligned16(dz) && unet_aligned16(gamma) && unet_aligned16(mean) &&
+                    unet_aligned16(invstd) && unet_aligned16(dgamma) && unet_aligned16(dbeta);
+    Plan pl;
+    UNET_CHECK_ARG(make_plan(P, C, C, ldr, lddz, al, &pl, true) && pl.vec == 8);      // (the plan unet_bn_bwd_any makes for a dense fp32 dy)
+    if (ws_bytes < unet_bn_workspace(P, C)) return UNET_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    double* part = (double*)ws;
+    // The grids of unet_bn_bwd_any (the block ranges decide the order of the sums), i.e. sized by the occupancy of the STORING kernels, not of
+    // the class-map forms launched here.  The trade: were a class-map form to fit fewer workgroups per CU, its launch would no longer be one
+    // resident wave (a tail, time only); today K <= 4 compiles to the storing kernels' register class (160 / 159 VGPRs against 160 / 176) and
+    // K <= 8 to 202 / 207, all two waves per SIMD.
+    int nb_r, nb_a;
+    bn_bwd_plain_grids(pl, &nb_r, &nb_a);
+    const long ppb_r = (P + nb_r - 1) / nb_r, ppb_a = (P + nb_a - 1) / nb_a;
+    const int vk = (lddzl == K && ((K == 4 && unet_aligned16(dz_logits)) || (K == 2 && (reinterpret_cast<uintptr_t>(dz_logits) & 7u) == 0))) ? 1 : 0;
+    if (K <= 4) bn_bwd_reduce_classmap_kernel<4><<<nb_r, 256, pl.smem2, st>>>(dz_logits, lddzl, w, K, r, ldr, mean, P, C, pl.tpp, ppb_r, part, vk);
+    else        bn_bwd_reduce_classmap_kernel<8><<<nb_r, 256, pl.smem2, st>>>(dz_logits, lddzl, w, K, r, ldr, mean, P, C, pl.tpp, ppb_r, part, vk);
+    int rc = UNET_LAUNCH_STATUS(); if (rc) return rc;
+    bn_bwd_finalize_kernel<<<C, 256, 0, st>>>(part, nb_r, C, invstd, dgamma, dbeta);
+    rc = UNET_LAUNCH_STATUS(); if (rc) return rc;
+    double* part2 = part + (size_t)2 * MAX_BLOCKS * C;
+    if (K <= 4) bn_bwd_apply_classmap_kernel<4><<<nb_a, 256, pl.smem1, st>>>(dz_logits, lddzl, w, K, r, ldr, gamma, mean, invstd, dgamma, dbeta,
+                                                                             P, C, pl.tpp, ppb_a, relu, dz, lddz, part2, vk);
+    else        bn_bwd_apply_classmap_kernel<8><<<nb_a, 256, pl.smem1, st>>>(dz_logits, lddzl, w, K, r, ldr, gamma, mean, invstd, dgamma, dbeta,
+                                                                             P, C, pl.tpp, ppb_a, relu, dz, lddz, part2, vk);
+    rc = UNET_LAUNCH_STATUS(); if (rc) return rc;
+    if (host_bias_rows) { *host_bias_rows = nb_a; return UNET_OK; }
+    colsum_finalize_kernel<<<C, 256, 0, st>>>(part2, nb_a, C, dbias);
+    return UNET_LAUNCH_STATUS();
 }
 
 // The bias gradient sum(dz) of a unet_bn_bwd_any call that was given host_bias_rows: `ws` is that call's workspace (untouched since),

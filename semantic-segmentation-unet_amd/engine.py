@@ -380,7 +380,8 @@ class Engine:
         lp = self.pl.layer[name]
         kind, cin, cout = lp.kind, lp.cin, lp.cout
         n, h, w, _ = x.shape
-        assert (h, w) == (lp.hi, lp.wi) and (in_view is not None) == lp.x_on_load and (y_out is None) == lp.defer_y, name
+        assert (h, w) == (lp.hi, lp.wi) and (in_view is not None) == (lp.x_on_load or lp.x_bn_on_load), name
+        assert (y_out is None) == (lp.defer_y or lp.y_in_classmap), name
         w_, b_ = self.p[name + "/kernel"], self.p[name + "/bias"]
         fused_stats = None
         r16 = lp.r == BF16
@@ -413,6 +414,9 @@ class Engine:
             fused_stats = (stat_part, rows) if rows > 0 else None
         elif kind == "deconv":
             L.unet_convT2x2_fwd(_p(x), _ld(x), _p(w_), _p(b_), _p(r), _ld(r), n, h, w, cin, cout, st)
+        elif kind == "conv1" and in_view is not None:       # x is dec_1b's conv output: its BatchNorm is applied on load (no y in memory)
+            self._timed("classmap_fwd", self._nb(x, r), L.unet_conv1x1_fwd_bn,
+                        _p(x), _ld(x), _p(in_view[0]), _p(in_view[1]), _p(w_), _p(b_), _p(r), cout, n * h * w, cin, cout, 1, st)
         elif kind == "conv1":
             self._timed("classmap_fwd", self._nb(x, r), L.unet_conv1x1_fwd,
                         _p(x), _ld(x), int(x.dtype == torch.bfloat16), _p(w_), _p(b_), _p(r), cout, n * h * w, cin, cout, 1, st)
@@ -624,8 +628,13 @@ class Engine:
                 f("up_%d" % lvl, cur, cat[..., ch:], training)
             # (dec_1b: the class-map conv computes in fp32, so storing its input as bf16 changes the result -- only the training step of
             # the mixed-precision mode does it (Keras mixed_bfloat16 semantics); inference keeps the fp32 tensor: plan.py)
-            cur = pair("dec_%da" % lvl, "dec_%db" % lvl, cat, cat_view, hh, ww, ch, ybuf("dec_%db" % lvl, (n, hh, ww, ch)))
-        yl = f("logits", cur, self._buf("y_logits", (n, h, w, self.K)), training)
+            last = pl.layer["dec_%db" % lvl]
+            cur = pair("dec_%da" % lvl, "dec_%db" % lvl, cat, cat_view, hh, ww, ch,
+                       None if last.y_in_classmap else ybuf("dec_%db" % lvl, (n, hh, ww, ch)))
+        # (y_in_classmap: cur is dec_1b's conv output and the class map applies its BatchNorm on load)
+        s1b = self.stat["dec_1b"]
+        yl = f("logits", cur, self._buf("y_logits", (n, h, w, self.K)), training,
+               in_view=(s1b[2][:B], s1b[3][:B]) if pl.layer["logits"].x_bn_on_load else None)
         prob = self._buf("softmax", (n, h, w, self.K))
         P = n * h * w
         nb = L.unet_softmax_ce_workspace(P)
@@ -662,8 +671,21 @@ class Engine:
         dz = self._buf("dz16_" + name, tuple(r.shape), torch.bfloat16) if dz16 else self._buf("dz_" + name, tuple(r.shape))
         pre = self.bnbwd_part.pop(name, None) if not eval_mode else None
         assert (pre is not None) == (lp.sums_from_dgrad and not eval_mode), name
+        assert (dy is None) == (lp.dy_from_classmap and not eval_mode), name
         bias_rows = None
-        if eval_mode:
+        if dy is None:
+            # the layer in front of the class map: dy = (class map's dz) . (class map's kernel)^T is formed inside both passes
+            # (unet_bn_bwd_classmap) -- the class map wrote no input gradient
+            assert pre is None and pool_grad is None and kind != "deconv"
+            dzl, wl = self.bufs["dz_logits"], self.p["logits/kernel"]
+            nb = L.unet_bn_workspace(P, cout)
+            bnws = self._buf("bnws_" + name, (int(nb) + 256,), torch.uint8)
+            bias_rows = ctypes.c_int(0)
+            self._timed("bn_bwd", 2 * self._nb(dzl, r) + self._nb(dz), L.unet_bn_bwd_classmap,
+                        _p(dzl), _ld(dzl), _p(wl), dzl.shape[3], n, ho, wo, _p(r), _ld(r),
+                        _p(self.p[name + "/gamma"]), _p(s[0]), _p(s[1]), cout, 1, _p(dz), cout,
+                        _p(self.g[name + "/gamma"]), _p(self.g[name + "/beta"]), None, _p(bnws), nb, st, ctypes.byref(bias_rows))
+        elif eval_mode:
             L.unet_bn_eval_bwd(_p(dy), _ld(dy), _p(r), _ld(r), _p(self.coef[name][0]), _p(dz), cout, P, cout, 0 if kind == "deconv" else 1, st)
         else:
             # one entry point for the three forms (plain / pooled / sums from the consumer's data gradient: no reduction pass), any of dy /
@@ -708,6 +730,11 @@ class Engine:
                 nb2 = L.unet_convT2x2_wgrad_workspace_wg(n, hi, wi, cin, cout, cap)
                 self._timed("convt_wgrad", 8.0 * n * hi * wi * cin * cout, L.unet_convT2x2_wgrad_wg,
                             _p(x), _ld(x), _p(dz), cout, _p(dw), n, hi, wi, cin, cout, cap, _p(self._workspace(nb2, sd)), nb2, st2)
+            elif kind == "conv1" and self.view.get(name) is not None:        # x is dec_1b's conv output, read through its BatchNorm
+                nb2 = L.unet_conv1x1_wgrad_workspace(P, cin, cout)
+                vw = self.view[name]
+                self._timed("classmap_wgrad", self._nb(x, dz), L.unet_conv1x1_wgrad_bn,
+                            _p(x), _ld(x), _p(vw[0]), _p(vw[1]), _p(dz), cout, _p(dw), P, cin, cout, _p(self._workspace(nb2, sd)), nb2, st2)
             elif kind == "conv1":
                 nb2 = L.unet_conv1x1_wgrad_workspace(P, cin, cout)
                 self._timed("classmap_wgrad", self._nb(x, dz), L.unet_conv1x1_wgrad,

@@ -40,6 +40,11 @@ class EngineOptions:
     bf16_storage: bool = True         # stage 2 (see module docstring)
     bf16_activations: bool = True     # stage 3
     overlap_wgrad: bool = True        # weight gradients on a side stream
+    # fp32 training step, the full-resolution tensors at the class-map end that are functions of things already in memory:
+    classmap_dy_on_load: bool = True  # dec_1b's BatchNorm backward forms its dy from the class map's dz and kernel (unet_bn_bwd_classmap): the class
+    #                                   map computes no input gradient
+    classmap_bn_on_load: bool = True  # the class map's forward and weight gradient read dec_1b's conv output through its BatchNorm coefficients
+    #                                   (unet_conv1x1_fwd_bn / _wgrad_bn): dec_1b's BatchNorm output is not materialised
     max_workgroups: Optional[int] = None     # cap on every persistent grid (the `_wg` entry points of include/unet_hip.h: Winograd forward / data /
     #                                   weight gradient, bf16 3x3 kernels, transposed-conv forward and weight gradients): None / 0 = one
     #                                   workgroup per CU, n = at most n workgroups (224 leaves ~4 CUs per XCD to a collective's kernels;
@@ -55,7 +60,8 @@ class EngineOptions:
         o.fp32_matrix = env.get("UNET_FP32_MATRIX", o.fp32_matrix)
         for name, var in (("bn_on_load", "UNET_BN_ON_LOAD"), ("fuse_bn_stats", "UNET_FUSE_BN_STATS"), ("fuse_pool", "UNET_FUSE_POOL"),
                           ("merge_bn_finalize", "UNET_MERGE_BN_FINALIZE"), ("bf16_storage", "UNET_BF16_STORAGE"), ("bf16_activations", "UNET_BF16_ACTIVATIONS"),
-                          ("overlap_wgrad", "UNET_OVERLAP_WGRAD")):
+                          ("overlap_wgrad", "UNET_OVERLAP_WGRAD"), ("classmap_dy_on_load", "UNET_CLASSMAP_DY_ON_LOAD"),
+                          ("classmap_bn_on_load", "UNET_CLASSMAP_BN_ON_LOAD")):
             if var in env:
                 setattr(o, name, env[var] != "0")
         if "UNET_MAX_WORKGROUPS" in env:
@@ -119,6 +125,10 @@ class LayerPlan:
     fwd_stats: bool = False        # BatchNorm sums of the output come from the forward kernel's epilogue
     sums_from_dgrad: bool = False  # BatchNorm-backward sums come from the consumer's data-gradient epilogue
     leaves_sums_for: Optional[Tuple[str, int, int]] = None     # (producer, c0, c1): this layer's data gradient leaves them
+    # the class-map end of an fp32 training step (kept apart from defer_y / x_on_load, which state the fused Winograd route's weight fold):
+    dy_from_classmap: bool = False # dec_1b: BatchNorm backward forms dy from the class map's dz and kernel (the class map has dx = None)
+    y_in_classmap: bool = False    # dec_1b: y = None, the class map applies this layer's BatchNorm on load
+    x_bn_on_load: bool = False     # logits: reads dec_1b's conv output through (scale, shift) in its forward and weight gradient
 
 
 @dataclass
@@ -140,7 +150,8 @@ class StepPlan:
             rows.append("%-8s %-6s %4d->%-4d @%dx%d  fwd=%-12s dgrad=%-11s wgrad=%-10s r=%s y=%s dz=%s dx=%s%s%s%s%s" % (
                 p.name, p.kind, p.cin, p.cout, p.ho, p.wo, p.fwd + ("/x6" if p.fwd_x6 else ""), p.dgrad + ("/x6" if p.dgrad_x6 else ""), p.wgrad, p.r, p.y, p.dz, p.dx,
                 " on_load" if p.x_on_load else "", " defer_y" if p.defer_y else "", " fwd_stats" if p.fwd_stats else "",
-                " sums<-" + CONSUMER.get(p.name, "?") if p.sums_from_dgrad else ""))
+                " sums<-" + CONSUMER.get(p.name, "?") if p.sums_from_dgrad else "")
+                + (" dy<-classmap" if p.dy_from_classmap else "") + (" y->classmap" if p.y_in_classmap else "") + (" bn_on_load" if p.x_bn_on_load else ""))
         rows.append("concat/pool storage: " + " ".join("L%d=%s%s" % (l, d, "(fused)" if self.fuse_pool[l] else "") for l, d in self.cat.items()))
         return "\n".join(rows)
 
@@ -304,6 +315,15 @@ def build_plan(opt, number_channels, number_classes, n, h, w, training, want_gra
                 pl.layer[a].defer_y, pl.layer[a].y, pl.layer[b].x_on_load = True, None, True
     if can_defer("bott_a", "bott_b"):
         pl.layer["bott_a"].defer_y, pl.layer["bott_a"].y, pl.layer["bott_b"].x_on_load = True, None, True
+
+    # ---- the class-map end of an fp32 training step: two full-resolution tensors that are never materialised ------------------------------
+    last, cm = pl.layer["dec_1b"], pl.layer["logits"]
+    ends = (train and bool(want_grad) and not bf and cm.kind == "conv1" and cm.cin == last.cout and 1 <= cm.cout <= 8 and last.cout % 8 == 0
+            and last.r == F32 and last.dz == F32)
+    if ends and opt.classmap_bn_on_load and last.y == F32:
+        last.y_in_classmap, last.y, cm.x_bn_on_load = True, None, True
+    if ends and opt.classmap_dy_on_load and 256 % (last.cout // 8) == 0:
+        last.dy_from_classmap, cm.dx = True, None
 
     # ---- backward: sums from data-gradient epilogues, storage of the data gradients ----------------------------------------------------------
     if train:
