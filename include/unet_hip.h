@@ -331,6 +331,23 @@ int unet_softmax_ce(const float* logits, int ldz, const int* labels_onehot, floa
 /* np.argmax(softmax, axis=-1), UNet/inference.py:107,166 (first maximum wins) */
 int unet_argmax(const float* p, int ldp, int* out, long P, int K, void* stream);
 
+/* ---- whole-image inference on the device: one upload, per tile gather -> forward -> paste, one mask download ------------------------
+ * tile_gather: the tiled driver's crop of the reflect-padded, z-scored image (UNet/inference.py:30-47,98-103; whole image :143-161;
+ *       z-score over the whole image :201-206 = UNet/imagereader.py:33-49) without either intermediate: img is the RAW image [H][W][C],
+ *       dtype 0 = uint8, 1 = uint16, 2 = fp32; out [1][C][th][tw] (the network's input contract) = ((float)src - mean[c]) / std[c], the
+ *       division correctly rounded as numpy's float32 one (the caller passes std[c] = 1 where the reader only subtracts the mean);
+ *       (y0, x0, th, tw) is the tile in padded-image coordinates, rows >= H / columns >= W read the np.pad(mode='reflect') source pixel
+ *       (period 2(n - 1), any number of reflections).  H == 1 or W == 1 with padding to read: UNET_EINVAL (no reflection exists).
+ * argmax_paste: np.argmax(softmax, axis=-1), the strip of the halo and the paste into the mask (UNet/inference.py:107-129; :166-171) in one
+ *       pass: prob is the tile's softmax [th][tw] with ldp floats per pixel; the zone (oy, ox, zh, zw) inside the tile is written to
+ *       mask[my + r][mx + c] (pitch in elements; elem_size 1 = uint8, needs K <= 256, or 4 = int32), first maximum wins exactly as in
+ *       unet_argmax.  Nothing outside the zone is touched and the zone is clipped against the mask extent (Hm, Wm), so a mask of the
+ *       unpadded size never receives the reflect padding (the crop of :131-135,168-171). */
+int unet_image_tile_gather(const void* img, int dtype, int H, int W, int C, const float* mean, const float* stddev,
+                           int y0, int x0, int th, int tw, float* out, void* stream);
+int unet_argmax_paste(const float* prob, int ldp, int th, int tw, int K, int oy, int ox, int zh, int zw,
+                      void* mask, int elem_size, long pitch, int my, int mx, int Hm, int Wm, void* stream);
+
 /* ---- eval-mode backward to the input image: the ERF probe of UNet.estimate_radius, UNet/model.py:165-202 ----------- */
 /* dlogits_k = p_k (g_k - sum_j g_j p_j); BN with moving statistics is affine: dz = dy*scale (times the ReLU mask);
  * data gradient of the first 3x3 layer (Cin = number_channels), which the training path never needs. */

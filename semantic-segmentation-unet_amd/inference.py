@@ -8,14 +8,23 @@ tile, halo stripped, pasted (:54-129); mask = argmax over classes, first maximum
 uint8/uint16/int32 by its maximum (:215-220), written as the reference's imsave call asks (:221-227): a deflate-compressed BigTIFF
 in 1024 x 1024 tiles (tifffile when importable, else the writer below).  The argmax runs on the device (`unet_argmax`).  Reading:
 .npy, or anything Pillow opens (the reference uses scikit-image, absent here).
+
+Two drivers compute the same mask.  `segment_image` (the default) keeps the image on the device: the raw image goes up once, every
+tile of `tile_plan` is cut out of the reflect padding, z-scored (`unet_image_tile_gather`), classified and pasted
+(`unet_argmax_paste`) on the current stream without a host synchronisation, and one narrow mask comes back; the file of image i is
+written by a worker thread while image i + 1 is segmented.  `_inference` / `_inference_tiling` (`host_pipeline=True`,
+`--host_pipeline`) are the reference's line-for-line host loop.
 """
 import argparse
+import ctypes
 import os
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 from . import model as unet_model_module
+from ._lib import lib
 from .readers import zscore_normalize
 
 TILE_SIZE = 1024
@@ -71,6 +80,115 @@ def _inference_tiling(img, unet, tile_size, predict=_predict):
             oy, ox = y0 - ty0, x0 - tx0
             mask[y0:y1, x0:x1] = pred[oy:oy + (y1 - y0), ox:ox + (x1 - x0)]
     return mask[:height - pad_y, :width - pad_x]
+
+
+def tile_plan(height, width, tile_size, radius, tiled=None):
+    """The (tile rect, zone rect) pairs the drivers above visit, in their order, for an image of `height` x `width` AFTER padding to a
+    multiple of 16; rects are (y0, x0, h, w) in padded-image coordinates.  Pure host arithmetic.
+
+    An image that fits in one tile is the single whole-image entry of `_inference` (`radius` is not looked at and may be None) -- the
+    dispatch of `inference()`.  Anything larger is `_inference_tiling`'s loop: zones of responsibility of tile_size - 2 * radius, a
+    halo of `radius` on every side that exists, and the reference's far-halo rule at the image edge (the far halo is dropped
+    entirely when the padded window would cross the edge, UNet/inference.py:86-96).  `tiled=True` returns that loop whatever the size
+    (what `_inference_tiling` does when called directly on an image between one zone and one tile), `tiled=False` the whole-image entry."""
+    assert height > 0 and width > 0 and height % SIZE_FACTOR == 0 and width % SIZE_FACTOR == 0
+    if tiled is None:
+        tiled = height > tile_size or width > tile_size
+    if not tiled:
+        return [((0, 0, height, width), (0, 0, height, width))]
+    assert tile_size % SIZE_FACTOR == 0 and radius % SIZE_FACTOR == 0
+    zone = tile_size - 2 * radius
+    assert zone >= radius
+    plan = []
+    for y0 in range(0, height, zone):
+        for x0 in range(0, width, zone):
+            y1, x1 = min(y0 + zone, height), min(x0 + zone, width)
+            ty0 = y0 - radius if y0 - radius >= 0 else 0
+            tx0 = x0 - radius if x0 - radius >= 0 else 0
+            ty1 = y0 + zone + radius if y0 + zone + radius <= height else height
+            tx1 = x0 + zone + radius if x0 + zone + radius <= width else width
+            plan.append(((ty0, tx0, ty1 - ty0, tx1 - tx0), (y0, x0, y1 - y0, x1 - x0)))
+    return plan
+
+
+_RAW_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.float32): 2}      # unet_image_tile_gather's dtype argument
+
+
+def _zscore_scalars(img_hwc):
+    """Per channel (mean, std) as float32, std = 1 where the reader only subtracts the mean (std <= 1, UNet/imagereader.py:33-49).  The
+    same numpy calls on the same contiguous float32 channel as `readers.zscore_normalize`, so the same scalars to the last bit."""
+    c = img_hwc.shape[2]
+    coef = np.empty((2, c), np.float32)
+    for k in range(c):
+        ch = np.ascontiguousarray(img_hwc[:, :, k], dtype=np.float32)
+        std, mean = float(np.std(ch)), float(np.mean(ch))
+        coef[0, k] = mean
+        coef[1, k] = 1.0 if std <= 1.0 else std
+    return coef
+
+
+def _segment_host_pipeline(raw, unet, tile_size=TILE_SIZE):
+    """the reference's loop (UNet/inference.py:201-213): float32, z-score over the whole image, whole-image or tiled driver"""
+    img = raw.astype(np.float32)
+    hwc = img[:, :, None] if img.ndim == 2 else img
+    img = zscore_normalize(hwc.transpose(2, 0, 1)).transpose(1, 2, 0)
+    if img.shape[0] > tile_size or img.shape[1] > tile_size:
+        return _inference_tiling(img, unet, tile_size)
+    return _inference(img, unet)
+
+
+def segment_image(img, unet, tile_size=TILE_SIZE, radius=None):
+    """Raw image (HW or HWC, any dtype `_read` returns) -> class map [H, W], the mask `_inference` / `_inference_tiling` compute on the
+    z-scored image, bit for bit, with the whole pipeline on the device: one upload of the image in its raw dtype (uint8 / uint16 / fp32;
+    anything else is converted to fp32 on the host first, as the host path does), then per entry of `tile_plan` gather (reflect padding,
+    z-score, NCHW) -> eval forward -> argmax + paste of the zone of responsibility, all on the current stream with no host
+    synchronisation in between, then one download of the mask and one synchronise.  The mask is uint8 when number_classes <= 256, else
+    int32 (the caller's `seg.astype(mask_dtype(seg.max()))` is unchanged).
+
+    The per-channel mean and std stay ONE HOST PASS over the image (`_zscore_scalars`: numpy's pairwise float32 summation picks the
+    scalars, and a device reduction cannot reproduce it bit for bit).  `radius`: None = `unet.estimate_radius()`, asked only when the
+    image is tiled.  An image with a one-pixel axis has no reflection to pad it with on the device and takes the host path (which asks
+    `unet.estimate_radius()` itself)."""
+    img = np.asarray(img)
+    if img.ndim not in (2, 3):
+        raise IOError("Invalid number of dimensions for input image. Expecting HW or HWC dimension ordering.")
+    if img.ndim == 2:
+        img = img[:, :, None]
+    if img.dtype not in _RAW_DTYPES:
+        img = img.astype(np.float32)
+    img = np.ascontiguousarray(img)
+    h, w, c = img.shape
+    hp, wp = h + (-h) % SIZE_FACTOR, w + (-w) % SIZE_FACTOR
+    if h == 1 or w == 1:                             # padded to 16: unet_image_tile_gather refuses it (UNET_EINVAL)
+        return _segment_host_pipeline(img, unet, tile_size)
+    e, L = unet.engine, lib()
+    dev = e.dev
+    tiled = hp > tile_size or wp > tile_size
+    if tiled and radius is None:
+        radius = unet.estimate_radius()
+    plan = tile_plan(hp, wp, tile_size, radius)
+    coef_host = torch.from_numpy(_zscore_scalars(img)).pin_memory()
+    raw_host = torch.from_numpy(img.reshape(-1).view(np.uint8)).pin_memory()
+    coef = coef_host.to(dev, non_blocking=True)
+    raw = raw_host.to(dev, non_blocking=True)
+    k = unet.number_classes
+    mdt = torch.uint8 if k <= 256 else torch.int32
+    mask = torch.empty((h, w), dtype=mdt, device=dev)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    tiles = {}
+    for (ty, tx, th, tw), (zy, zx, zh, zw) in plan:
+        x = tiles.get((th, tw))
+        if x is None:
+            x = tiles[(th, tw)] = torch.empty((1, c, th, tw), dtype=torch.float32, device=dev)
+        st = e._stream()
+        L.unet_image_tile_gather(ptr(raw), _RAW_DTYPES[img.dtype], h, w, c, ptr(coef[0]), ptr(coef[1]), ty, tx, th, tw, ptr(x), st)
+        prob = e.forward(x, training=False)
+        L.unet_argmax_paste(ptr(prob), k, th, tw, k, zy - ty, zx - tx, zh, zw, ptr(mask), mask.element_size(), w, zy, zx, h, w, st)
+    out = torch.empty((h, w), dtype=mdt, pin_memory=True)
+    out.copy_(mask, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    del raw_host, coef_host                          # (pinned sources of the two uploads: alive until the synchronise above)
+    return out.numpy()
 
 
 def _read(path):
@@ -156,22 +274,30 @@ def mask_dtype(max_label):
     return np.int32
 
 
-def inference(checkpoint_filepath, image_folder, output_folder, number_classes, number_channels, image_format, compute_dtype=None):
+def inference(checkpoint_filepath, image_folder, output_folder, number_classes, number_channels, image_format, compute_dtype=None,
+              host_pipeline=False):
+    """host_pipeline: the reference's host loop per tile (`_inference` / `_inference_tiling`) instead of `segment_image`; the masks are
+    the same.  The file of image i is written by one worker thread while image i + 1 is segmented: files appear in order, every write
+    has finished when this returns, and the first exception of a write is raised here."""
     os.makedirs(output_folder, exist_ok=True)
     names = sorted(f for f in os.listdir(image_folder) if f.endswith("." + image_format))
     unet = unet_model_module.UNet(number_classes, 1, number_channels, 1e-4, compute_dtype=compute_dtype)
     unet.load_checkpoint(checkpoint_filepath)
-    for i, name in enumerate(names):
-        print("{}/{}".format(i, len(names)))
-        img = _read(os.path.join(image_folder, name)).astype(np.float32)
-        hwc = img[:, :, None] if img.ndim == 2 else img
-        img = zscore_normalize(hwc.transpose(2, 0, 1)).transpose(1, 2, 0)
-        if img.shape[0] > TILE_SIZE or img.shape[1] > TILE_SIZE:
-            seg = _inference_tiling(img, unet, TILE_SIZE)
-        else:
-            seg = _inference(img, unet)
-        seg = seg.astype(mask_dtype(int(seg.max())))
-        _write(os.path.join(output_folder, name), seg, image_format)
+    writer = ThreadPoolExecutor(max_workers=1)
+    writes = []
+    try:
+        for i, name in enumerate(names):
+            print("{}/{}".format(i, len(names)))
+            raw = _read(os.path.join(image_folder, name))
+            seg = _segment_host_pipeline(raw, unet) if host_pipeline else segment_image(raw, unet)
+            seg = seg.astype(mask_dtype(int(seg.max())))
+            if writes and writes[-1].done() and writes[-1].exception() is not None:
+                break                                 # a write has failed: segment no further images, report it below
+            writes.append(writer.submit(_write, os.path.join(output_folder, name), seg, image_format))
+    finally:
+        writer.shutdown(wait=True)                    # drain: every submitted write has run (or failed) before this returns
+    for f in writes:
+        f.result()                                    # re-raises the first exception of a write, in file order
 
 
 def main(argv=None):
@@ -184,9 +310,11 @@ def main(argv=None):
     ap.add_argument("--image_format", dest="image_format", type=str, default="tif")
     ap.add_argument("--compute_dtype", choices=["fp32", "bf16"], default=None,
                     help="opt-in extra: bf16 = mixed-precision contractions (fp32 is the reference's arithmetic and the default)")
+    ap.add_argument("--host_pipeline", dest="host_pipeline", action="store_true",
+                    help="cut, normalise, argmax and paste every tile on the host (the reference's loop) instead of on the device; same masks")
     a = ap.parse_args(argv)
     inference(a.checkpoint_filepath, a.image_folder, a.output_folder, a.number_classes, a.number_channels, a.image_format,
-              compute_dtype=a.compute_dtype)
+              compute_dtype=a.compute_dtype, host_pipeline=a.host_pipeline)
 
 
 if __name__ == "__main__":
