@@ -482,6 +482,54 @@ class OracleUNet:
         dimg, _ = b("conv_1a", d, du)
         return loss, softmax, g, c, dimg
 
+    def input_gradient_eval(self, images, dprob, relu_masks=None, pool_idx=None, prob=None, bf16_dgrad=False, keep=None, cache=None):
+        """d sum(dprob * softmax) / d images [N,C,H,W] with the graph in eval mode (tf.GradientTape().gradient(loss, img) of
+        UNet.estimate_radius, UNet/model.py:176-184): BatchNorm uses its moving statistics -- an affine map, dr = dy * gamma /
+        sqrt(moving_var + eps) -- and nothing drops out.
+        relu_masks / pool_idx replace the oracle's own decisions in the backward pass, as in loss_and_grads.  prob [N,H,W,K], if given,
+        replaces the oracle's own softmax at the start of the backward pass: with all three imposed the result is the LINEAR backward
+        map of another evaluation's forward pass (the bf16 mode's, whose forward values are far from this one's).
+        bf16_dgrad: a model of that mode's data gradients -- dz and the kernel of every 3x3 and transposed-conv data gradient rounded
+        to bf16, products exact, wide accumulation; everything else as before.
+        keep: a dict that receives "dz_<layer>" / "dx_<layer>" (NCHW) of every layer.
+        cache: the second result of forward(images, training=False), if the caller has it already (it is not modified)."""
+        assert self.plan is None, "the eval-mode gradient is stated for the fp32 contract; bf16_dgrad models the other mode's backward"
+        c = dict(cache) if cache is not None else self.forward(images, training=False)[1]
+        if pool_idx is not None:
+            c.update(pool_idx)
+        P, eps = self.params, self.contract.bn_eps
+        L = {n: k for n, k, _, _ in self.layers}
+        p = softmax_lastaxis(c["logits_nhwc"]) if prob is None else np.asarray(prob, self.dtype)
+        g = np.asarray(dprob, self.dtype)
+        dl = p * (g - (g * p).sum(axis=-1, keepdims=True))             # softmax backward: dz_k = p_k (g_k - sum_j g_j p_j)
+
+        def b(name, dy):
+            x, r, _ = c[name]
+            kind, w = L[name], P[name + "/kernel"]
+            dz = dy * (P[name + "/gamma"] / np.sqrt(P[name + "/moving_var"] + eps))[None, :, None, None]
+            if kind != "deconv":
+                dz = dz * (relu_masks[name] if relu_masks is not None else (r > 0))
+            if bf16_dgrad and kind != "conv1":
+                dzc, w = bf16_round(dz), bf16_round(w)
+            else:
+                dzc = dz
+            dx = deconv2x2_bwd(x, w, dzc)[0] if kind == "deconv" else conv_same_bwd(x, w, dzc)[0]
+            if keep is not None:
+                keep["dz_" + name], keep["dx_" + name] = dz, dx
+            return dx
+
+        d = b("logits", np.ascontiguousarray(dl.transpose(0, 3, 1, 2)))
+        skip = {}
+        for lvl, ch in ((1, BASE), (2, 2 * BASE), (3, 4 * BASE), (4, 8 * BASE)):
+            d = b("dec_%da" % lvl, b("dec_%db" % lvl, d))
+            skip[lvl] = d[:, :ch]
+            d = b("up_%d" % lvl, np.ascontiguousarray(d[:, ch:]))
+        d = b("bott_a", b("bott_b", d))
+        for lvl in (4, 3, 2, 1):
+            d = maxpool2x2_bwd(d, c["pool_%d" % lvl]) + skip[lvl]
+            d = b("conv_%da" % lvl, b("conv_%db" % lvl, d))
+        return d
+
     def train_step(self, images, labels, dropout_masks):
         """UNet.train_step (UNet/model.py:204-228): forward, loss, grads, Adam apply, BN moving-stat update."""
         loss, softmax, g, c, _ = self.loss_and_grads(images, labels, dropout_masks)

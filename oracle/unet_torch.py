@@ -143,10 +143,10 @@ class TorchUNet:
             softmax, _, _ = self.forward(images, False)
         return np.argmax(softmax.cpu().numpy(), axis=-1).astype(np.int32)
 
-    def input_gradient_eval(self, images, dprob):
-        """d sum(dprob * softmax) / d image with the graph in eval mode (autograd)."""
+    def input_gradient_eval(self, images, dprob, relu_masks=None):
+        """d sum(dprob * softmax) / d image with the graph in eval mode (autograd).  relu_masks: as in forward()."""
         x = torch.as_tensor(np.asarray(images)).to(self.dtype).to(self.device).requires_grad_(True)
-        softmax, _, _ = self.forward(x, False)
+        softmax, _, _ = self.forward(x, False, relu_masks=relu_masks)
         (softmax * torch.as_tensor(np.asarray(dprob)).to(self.dtype).to(self.device)).sum().backward()
         return x.grad.detach().cpu().numpy()
 
@@ -163,6 +163,7 @@ class TorchUNet:
         g = np.average(g, axis=0) if g.shape[0] > 1 else g[0]
         vec = np.maximum(np.max(g, axis=0), np.max(g, axis=1))
         idx = np.nonzero(vec > 1e-8)[0]
+        self.erf_extent = (int(idx.min()), int(idx.max())) if len(idx) >= 2 else None     # None: the fallback below was taken
         if len(idx) < 2:
             return on.RADIUS
         erf = int((np.max(idx) - np.min(idx)) / 2)

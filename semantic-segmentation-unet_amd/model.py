@@ -171,11 +171,12 @@ class UNet:
         x = torch.as_tensor(img)
         prob = self.engine.forward(x, training=False)
         k = prob.shape[-1]
-        # loss[h,w] = mean_k |msk - p| is non-zero only at the centre pixel, where msk = 1 - p:
-        # d/dp_k of mean_k |1 - 2 p_k| = -2 sign(1 - 2 p_k) / K
+        # loss[h,w] = mean_k |msk - p| is non-zero only at the centre pixel, where msk = 1 - p.  msk is a CONSTANT of the tape (the
+        # reference takes it from softmax.numpy()), so d/dp_k of mean_k |msk_k - p_k| = -sign(msk_k - p_k) / K = -sign(1 - 2 p_k) / K --
+        # not the derivative of |1 - 2 p_k|, which is twice that and widens the extent of |grad| > 1e-8
         g = torch.zeros_like(prob)
         pm = prob[0, mid, mid, :]
-        g[0, mid, mid, :] = -2.0 * torch.sign(1.0 - 2.0 * pm) / k
+        g[0, mid, mid, :] = -torch.sign(1.0 - 2.0 * pm) / k
         grad_img = np.abs(self.engine.input_gradient_eval(g)[0].cpu().numpy())      # [C,H,W]
         grad_img = np.average(grad_img, axis=0) if self.number_channels > 1 else grad_img[0]
         print('Theoretical RF: {}'.format(UNet.RADIUS))

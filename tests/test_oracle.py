@@ -116,6 +116,73 @@ def test_finite_difference_gradient_fp64():
         assert abs(fd - g[key][idx]) <= 1e-4 * max(abs(fd), abs(g[key][idx])) + 2e-8, (key, fd, g[key][idx])
 
 
+def _eval_case(seed, n, c, k, h, w):
+    """tests/test_gpu_unet.py's make_case without the dropout masks: every per-channel parameter, the moving statistics included, random"""
+    rng = np.random.default_rng(seed)
+    img, _ = on.synthetic_batch(n, c, k, h, w, seed=seed)
+    P = on.init_params(c, k, seed=seed)
+    for key in P:
+        if key.endswith(("bias", "beta")):
+            P[key] = rng.normal(0, 0.1, P[key].shape).astype(np.float32)
+        if key.endswith("gamma"):
+            P[key] = rng.uniform(0.5, 1.5, P[key].shape).astype(np.float32)
+        if key.endswith("moving_mean"):
+            P[key] = rng.normal(0.3, 0.1, P[key].shape).astype(np.float32)
+        if key.endswith("moving_var"):
+            P[key] = rng.uniform(0.5, 1.5, P[key].shape).astype(np.float32)
+    return img, P, rng.standard_normal((n, h, w, k))
+
+
+@pytest.mark.parametrize("cfg", [(1, 3, 4, 32, 32), (2, 1, 2, 32, 48)])
+def test_eval_input_gradient_matches_torch_autograd_fp64(cfg):
+    # the hand-written eval-mode backward chain (softmax, affine BatchNorm, ReLU masks, data gradients, pool + skip) against autograd
+    n, c, k, h, w = cfg
+    img, P, dprob = _eval_case(11, n, c, k, h, w)
+    o = on.OracleUNet(k, n, c, params=P, dtype=np.float64)
+    t = ot.TorchUNet(k, n, c, params=P, dtype=torch.float64)
+    keep = {}
+    g = o.input_gradient_eval(img, dprob, keep=keep)
+    g_ref = t.input_gradient_eval(img, dprob)
+    assert g.shape == g_ref.shape == (n, c, h, w) and np.linalg.norm(g_ref) > 0
+    assert np.linalg.norm(g - g_ref) <= 1e-9 * np.linalg.norm(g_ref)
+    assert len(keep) == 2 * len(o.layers) and keep["dx_conv_1a"] is g
+    # its own decisions and softmax handed back in: the same gradient, bit for bit (numpy), and no decision overridden (torch)
+    sm, cache = o.forward(img, training=False)
+    relu = {name: cache[name][1] > 0 for name, kind, _, _ in o.layers if kind != "deconv"}
+    pidx = {"pool_%d" % l: cache["pool_%d" % l] for l in (1, 2, 3, 4)}
+    assert np.array_equal(o.input_gradient_eval(img, dprob, relu_masks=relu, pool_idx=pidx, prob=sm, cache=cache), g)
+    assert np.linalg.norm(t.input_gradient_eval(img, dprob, relu_masks=relu) - g_ref) <= 1e-12 * np.linalg.norm(g_ref)
+    assert len(t.imposed_flips) == len(relu) and not any(t.imposed_flips.values())
+    # the imposed decisions are what the backward pass uses: another image's ReLU masks, pool winners or softmax give another gradient
+    sm2, other = o.forward(img[:, :, ::-1].copy(), training=False)
+    far = lambda a: np.linalg.norm(a - g) > 1e-2 * np.linalg.norm(g)
+    assert far(o.input_gradient_eval(img, dprob, relu_masks={name: other[name][1] > 0 for name in relu}, cache=cache))
+    assert far(o.input_gradient_eval(img, dprob, pool_idx={key: other[key] for key in pidx}, cache=cache))
+    assert far(o.input_gradient_eval(img, dprob, prob=sm2, cache=cache))
+    # the model of the bf16 mode's data gradients moves it by a few bf16 ulps' worth, not more
+    e16 = np.linalg.norm(o.input_gradient_eval(img, dprob, bf16_dgrad=True, cache=cache) - g) / np.linalg.norm(g)
+    assert 2.0 ** -12 < e16 < 2.0 ** -5, e16
+
+
+def test_eval_input_gradient_matches_central_differences_fp64():
+    # six seeded pixels, two of them forced onto the border (a corner and an edge): the 'same' padding of the first-layer data gradient
+    n, c, k, h, w = 1, 3, 4, 32, 32
+    img, P, dprob = _eval_case(13, n, c, k, h, w)
+    o = on.OracleUNet(k, n, c, params=P, dtype=np.float64)
+    g = o.input_gradient_eval(img, dprob)
+    rng = np.random.default_rng(2)
+    pix = [(0, int(rng.integers(c)), 0, w - 1), (0, int(rng.integers(c)), int(rng.integers(1, h - 1)), 0)]
+    pix += [(0, int(rng.integers(c)), int(rng.integers(1, h - 1)), int(rng.integers(1, w - 1))) for _ in range(4)]
+    x = img.astype(np.float64)
+    step = 1e-6                 # the net is piecewise linear: the only error of a central difference is rounding, unless the step crosses a kink
+    for idx in pix:
+        xp, xm = x.copy(), x.copy()
+        xp[idx] += step
+        xm[idx] -= step
+        fd = (dprob * (o.forward(xp, training=False)[0] - o.forward(xm, training=False)[0])).sum() / (2 * step)
+        assert abs(fd - g[idx]) <= 1e-5 * max(abs(fd), abs(g[idx])), (idx, fd, g[idx])
+
+
 def test_train_step_and_eval_match_between_restatements():
     img, lab, P, masks = _small_case(seed=7)
     o = on.OracleUNet(2, 2, 1, params=P, dtype=np.float64)
