@@ -28,7 +28,9 @@ extern "C" {
 #define UNET_ENOSPC (-2)
 
 /* Bumped whenever an exported signature changes; a loader must refuse a library whose unet_hip_abi_version() differs
- * (8: round 6 -- + unet_bn_finalize_apply_any (statistics finalize merged into the apply launch); the bf16 3x3 kernels start their accumulators at the bias;
+ * (9: + unet_convT2x2_dgrad_x6_sums (the BF16x6 transposed-conv data gradient leaves the producer layer's BatchNorm-backward sums); added under 9 without a
+ *  bump, because no existing signature changed and a loader binds by name: unet_confusion_scores, unet_confusion_masks (per-class metrics);
+ *  8: round 6 -- + unet_bn_finalize_apply_any (statistics finalize merged into the apply launch); the bf16 3x3 kernels start their accumulators at the bias;
  *  7: round 5 -- no signature changed, but the operand unet_winograd_weight_transform_x6 / _fold_x6 write is laid out for the round-5 kernel
  *  (MFMA A-operand order per 64-channel tile, chunk and point row): an operand and the conv entry point that reads it must come from one library;
  *  6: round 4 -- unet_convT2x2_*_x6; 5: round 4 -- the `_wg` (max_workgroups) entry points of every persistent kernel, unet_standin_collective; 4: round 4 -- the BF16x6 Winograd route: unet_*_x6; 3: + deferred bias gradient of unet_bn_bwd_any; 2: round 3 -- max_workgroups of the fused Winograd weight gradient; 1: rounds 1-2). */
@@ -347,6 +349,21 @@ int unet_image_tile_gather(const void* img, int dtype, int H, int W, int C, cons
                            int y0, int x0, int th, int tw, float* out, void* stream);
 int unet_argmax_paste(const float* prob, int ldp, int th, int tw, int K, int oy, int ox, int zh, int zw,
                       void* mask, int elem_size, long pitch, int my, int mx, int Hm, int Wm, void* stream);
+
+/* ---- per-class segmentation metrics: the K x K confusion matrix behind IoU / Dice / precision / recall (csrc/metrics.hip; the reference reports
+ * pixel accuracy only, UNet/train.py:106,108) ----------------------------------------------------------------------------------------------
+ * Both calls ACCUMULATE into the caller's cm[K][K] of unsigned 64-bit counts, row = truth class, column = predicted class (8-byte aligned,
+ * zeroed by the caller); 1 <= K <= 1024.  All counting is in integers: the result is independent of launch order and of the path taken.
+ * confusion_scores: prediction = FIRST maximum of scores[p * lds .. + K) (start at class 0, replace on v > m: unet_argmax / unet_softmax_ce),
+ *       truth = first maximum of the one-hot row (an all-zero row counts as class 0), so trace(cm) == the correct_out of unet_softmax_ce on the
+ *       same logits and labels, exactly.  (Pass the LOGITS: a rounded softmax can tie where they do not.)
+ * confusion_masks: predicted class map (pred_elem 1 = uint8 or 4 = int32, the masks unet_argmax_paste writes) against a ground-truth class map
+ *       (truth_elem 1 = uint8, 2 = uint16, 4 = int32), H x W, pitches in elements.  A pixel whose truth == ignore_label is skipped (-1: nothing is);
+ *       a pixel whose truth is negative or >= K, or whose prediction is not in [0, K), is left out of cm and counted in *out_of_range (one
+ *       unsigned 64-bit word, 8-byte aligned, may be NULL, else zeroed by the caller: the convention of unet_labels_onehot). */
+int unet_confusion_scores(const float* scores, int lds, const int* labels_onehot, long P, int K, void* cm, void* stream);
+int unet_confusion_masks(const void* pred, int pred_elem, long pred_pitch, const void* truth, int truth_elem, long truth_pitch,
+                         int H, int W, int K, int ignore_label, void* cm, void* out_of_range, void* stream);
 
 /* ---- eval-mode backward to the input image: the ERF probe of UNet.estimate_radius, UNet/model.py:165-202 ----------- */
 /* dlogits_k = p_k (g_k - sum_j g_j p_j); BN with moving statistics is affine: dz = dy*scale (times the ReLU mask);

@@ -542,10 +542,14 @@ class Engine:
         return out
 
     def forward(self, images, training=False, dropout_masks=None, labels=None, global_batch_size=None,
-                label_smoothing=0.0, want_grad=False):
+                label_smoothing=0.0, want_grad=False, confusion=None):
         """images: fp32 [N,C,H,W] (reference input contract, UNet/imagereader.py:298-300).  Returns softmax [N,H,W,K]
         (a device tensor owned by the engine; valid until the next call).  With labels (int32 one-hot [N,H,W,K]) the
-        loss and the count of correctly classified pixels land in self.loss_buf."""
+        loss and the count of correctly classified pixels land in self.loss_buf.  confusion (metrics.ConfusionMatrix, needs labels): the
+        step's K x K counts are added to it by one more launch behind the loss kernel, on the same stream, from the LOGITS and the labels the
+        step already holds (its trace is the count in loss_buf[1]); None = not one extra launch."""
+        if confusion is not None and labels is None:
+            raise ValueError("a confusion matrix needs labels")
         L, st = self.L, self._stream()
         x = images
         assert x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == self.C, "images must be fp32 [N,C,H,W]"
@@ -651,6 +655,8 @@ class Engine:
                         _p(yl), self.K, _p(lab), _p(prob), _p(dl), self.K, P, self.K, float(label_smoothing), scale,
                         scale, float(self.ce_clip_eps), _p(self.loss_buf[0:1]), _p(self.loss_buf[1:2]), _p(ws), nb, st)
             self._labels_keepalive = lab
+            if confusion is not None:
+                self._timed("confusion", self._nb(yl, lab), confusion.update_from_scores, yl, lab, st)
         return prob
 
     # ------------------------------------------------------------------------------------------------ backward

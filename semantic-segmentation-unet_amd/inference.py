@@ -127,17 +127,50 @@ def _zscore_scalars(img_hwc):
     return coef
 
 
-def _segment_host_pipeline(raw, unet, tile_size=TILE_SIZE):
-    """the reference's loop (UNet/inference.py:201-213): float32, z-score over the whole image, whole-image or tiled driver"""
+def _check_truth(truth, confusion, h, w):
+    """the ground-truth class map of an h x w image as a contiguous uint8 / uint16 / int32 array (anything else is converted to int32)"""
+    if truth is None or confusion is None:
+        raise ValueError("scoring needs both `truth` and `confusion`")
+    truth = np.asarray(truth)
+    if truth.dtype.kind not in "iu":
+        raise ValueError("the ground-truth class map must have an integer dtype, not %s" % truth.dtype)
+    if truth.shape != (h, w):
+        raise ValueError("the ground-truth class map is %s, the image %s" % (truth.shape, (h, w)))
+    if truth.dtype not in (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.int32)):
+        truth = truth.astype(np.int32)
+    return np.ascontiguousarray(truth)
+
+
+def _host_confusion(mask, truth, confusion, ignore_label=-1):
+    """what `unet_confusion_masks` counts, with np.bincount on the host: rows = truth, columns = prediction; truth == ignore_label is
+    skipped (-1: nothing is), labels outside [0, K) go to confusion.out_of_range"""
+    k = confusion.number_classes
+    t, p = np.asarray(truth).astype(np.int64).ravel(), np.asarray(mask).astype(np.int64).ravel()
+    keep = np.ones(t.shape, bool) if ignore_label == -1 else t != ignore_label
+    inside = (t >= 0) & (t < k) & (p >= 0) & (p < k)
+    sel = keep & inside
+    confusion.add_counts(np.bincount(t[sel] * k + p[sel], minlength=k * k).reshape(k, k))
+    confusion.out_of_range += int((keep & ~inside).sum())
+
+
+def _segment_host_pipeline(raw, unet, tile_size=TILE_SIZE, truth=None, confusion=None, ignore_label=-1):
+    """the reference's loop (UNet/inference.py:201-213): float32, z-score over the whole image, whole-image or tiled driver.  With
+    truth / confusion the mask is scored on the host (the counts `segment_image` takes on the device)."""
+    if truth is not None or confusion is not None:
+        truth = _check_truth(truth, confusion, raw.shape[0], raw.shape[1])
     img = raw.astype(np.float32)
     hwc = img[:, :, None] if img.ndim == 2 else img
     img = zscore_normalize(hwc.transpose(2, 0, 1)).transpose(1, 2, 0)
     if img.shape[0] > tile_size or img.shape[1] > tile_size:
-        return _inference_tiling(img, unet, tile_size)
-    return _inference(img, unet)
+        mask = _inference_tiling(img, unet, tile_size)
+    else:
+        mask = _inference(img, unet)
+    if confusion is not None:
+        _host_confusion(mask, truth, confusion, ignore_label)
+    return mask
 
 
-def segment_image(img, unet, tile_size=TILE_SIZE, radius=None):
+def segment_image(img, unet, tile_size=TILE_SIZE, radius=None, truth=None, confusion=None, ignore_label=-1):
     """Raw image (HW or HWC, any dtype `_read` returns) -> class map [H, W], the mask `_inference` / `_inference_tiling` compute on the
     z-scored image, bit for bit, with the whole pipeline on the device: one upload of the image in its raw dtype (uint8 / uint16 / fp32;
     anything else is converted to fp32 on the host first, as the host path does), then per entry of `tile_plan` gather (reflect padding,
@@ -148,7 +181,13 @@ def segment_image(img, unet, tile_size=TILE_SIZE, radius=None):
     The per-channel mean and std stay ONE HOST PASS over the image (`_zscore_scalars`: numpy's pairwise float32 summation picks the
     scalars, and a device reduction cannot reproduce it bit for bit).  `radius`: None = `unet.estimate_radius()`, asked only when the
     image is tiled.  An image with a one-pixel axis has no reflection to pad it with on the device and takes the host path (which asks
-    `unet.estimate_radius()` itself)."""
+    `unet.estimate_radius()` itself).
+
+    truth + confusion (both or neither): a host ground-truth class map [H, W] of any integer dtype (uint8 / uint16 / int32 go up as they
+    are, beside the image, from pinned memory; the rest as int32) and a metrics.ConfusionMatrix.  After the last paste ONE
+    `unet_confusion_masks` launch on the same stream scores the device mask -- before the download's synchronise, still the only one --
+    and adds the K x K counts to `confusion` (truth == ignore_label skipped, -1 skips nothing; labels outside [0, K) counted in
+    confusion.out_of_range).  The returned mask is unchanged by it."""
     img = np.asarray(img)
     if img.ndim not in (2, 3):
         raise IOError("Invalid number of dimensions for input image. Expecting HW or HWC dimension ordering.")
@@ -158,11 +197,18 @@ def segment_image(img, unet, tile_size=TILE_SIZE, radius=None):
         img = img.astype(np.float32)
     img = np.ascontiguousarray(img)
     h, w, c = img.shape
+    scoring = truth is not None or confusion is not None
+    if scoring:
+        truth = _check_truth(truth, confusion, h, w)
     hp, wp = h + (-h) % SIZE_FACTOR, w + (-w) % SIZE_FACTOR
     if h == 1 or w == 1:                             # padded to 16: unet_image_tile_gather refuses it (UNET_EINVAL)
-        return _segment_host_pipeline(img, unet, tile_size)
+        return _segment_host_pipeline(img, unet, tile_size, truth=truth, confusion=confusion, ignore_label=ignore_label)
     e, L = unet.engine, lib()
     dev = e.dev
+    if scoring and (confusion.device != torch.empty(0, device=dev).device or confusion.number_classes != unet.number_classes):
+        # (checked here: the kernel takes the matrix by pointer, and a host matrix -- legal for add_counts -- would be a fault on the device)
+        raise ValueError("the confusion matrix must live on the network's device (%s, not %s) and count its %d classes (not %d)"
+                         % (dev, confusion.device, unet.number_classes, confusion.number_classes))
     tiled = hp > tile_size or wp > tile_size
     if tiled and radius is None:
         radius = unet.estimate_radius()
@@ -171,6 +217,9 @@ def segment_image(img, unet, tile_size=TILE_SIZE, radius=None):
     raw_host = torch.from_numpy(img.reshape(-1).view(np.uint8)).pin_memory()
     coef = coef_host.to(dev, non_blocking=True)
     raw = raw_host.to(dev, non_blocking=True)
+    if scoring:
+        truth_host = torch.from_numpy(truth.reshape(-1).view(np.uint8)).pin_memory()
+        truth_dev = truth_host.to(dev, non_blocking=True).view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[truth.dtype.itemsize]).view(h, w)
     k = unet.number_classes
     mdt = torch.uint8 if k <= 256 else torch.int32
     mask = torch.empty((h, w), dtype=mdt, device=dev)
@@ -184,10 +233,14 @@ def segment_image(img, unet, tile_size=TILE_SIZE, radius=None):
         L.unet_image_tile_gather(ptr(raw), _RAW_DTYPES[img.dtype], h, w, c, ptr(coef[0]), ptr(coef[1]), ty, tx, th, tw, ptr(x), st)
         prob = e.forward(x, training=False)
         L.unet_argmax_paste(ptr(prob), k, th, tw, k, zy - ty, zx - tx, zh, zw, ptr(mask), mask.element_size(), w, zy, zx, h, w, st)
+    if scoring:
+        confusion.update_from_masks(mask, truth_dev, ignore_label, st)
     out = torch.empty((h, w), dtype=mdt, pin_memory=True)
     out.copy_(mask, non_blocking=True)
     torch.cuda.current_stream().synchronize()
-    del raw_host, coef_host                          # (pinned sources of the two uploads: alive until the synchronise above)
+    del raw_host, coef_host                          # (pinned sources of the uploads: alive until the synchronise above)
+    if scoring:
+        del truth_host
     return out.numpy()
 
 
@@ -275,21 +328,42 @@ def mask_dtype(max_label):
 
 
 def inference(checkpoint_filepath, image_folder, output_folder, number_classes, number_channels, image_format, compute_dtype=None,
-              host_pipeline=False):
+              host_pipeline=False, mask_folder=None, ignore_label=-1):
     """host_pipeline: the reference's host loop per tile (`_inference` / `_inference_tiling`) instead of `segment_image`; the masks are
     the same.  The file of image i is written by one worker thread while image i + 1 is segmented: files appear in order, every write
-    has finished when this returns, and the first exception of a write is raised here."""
+    has finished when this returns, and the first exception of a write is raised here.
+
+    mask_folder (opt-in extra): ground-truth class maps with the images' file names.  Every mask is scored against its ground truth
+    (on the device, or on the host with host_pipeline: the same counts) and the output folder also receives `scores.csv` -- one row per
+    image and a final `total` row: image, pixel_accuracy, mean_iou, iou_0.., dice_0.. -- and `confusion.npy`, the summed int64 matrix
+    (rows = truth).  A missing ground-truth file is an error before anything is segmented."""
     os.makedirs(output_folder, exist_ok=True)
     names = sorted(f for f in os.listdir(image_folder) if f.endswith("." + image_format))
+    if mask_folder is not None:
+        for name in names:
+            if not os.path.isfile(os.path.join(mask_folder, name)):
+                raise FileNotFoundError("no ground-truth mask for image %s: %s is missing" % (name, os.path.join(mask_folder, name)))
     unet = unet_model_module.UNet(number_classes, 1, number_channels, 1e-4, compute_dtype=compute_dtype)
     unet.load_checkpoint(checkpoint_filepath)
+    score_rows, total = [], np.zeros((number_classes, number_classes), np.int64)
+    if mask_folder is not None:
+        from . import metrics
+        per_image = metrics.ConfusionMatrix(number_classes, device=unet.engine.dev)
     writer = ThreadPoolExecutor(max_workers=1)
     writes = []
     try:
         for i, name in enumerate(names):
             print("{}/{}".format(i, len(names)))
             raw = _read(os.path.join(image_folder, name))
-            seg = _segment_host_pipeline(raw, unet) if host_pipeline else segment_image(raw, unet)
+            kw = {}
+            if mask_folder is not None:
+                per_image.reset_states()
+                kw = dict(truth=_read(os.path.join(mask_folder, name)), confusion=per_image, ignore_label=ignore_label)
+            seg = _segment_host_pipeline(raw, unet, **kw) if host_pipeline else segment_image(raw, unet, **kw)
+            if mask_folder is not None:
+                counts = per_image.result()
+                total += counts
+                score_rows.append(metrics.csv_row(name, metrics.summarize(counts)))
             seg = seg.astype(mask_dtype(int(seg.max())))
             if writes and writes[-1].done() and writes[-1].exception() is not None:
                 break                                 # a write has failed: segment no further images, report it below
@@ -298,6 +372,11 @@ def inference(checkpoint_filepath, image_folder, output_folder, number_classes, 
         writer.shutdown(wait=True)                    # drain: every submitted write has run (or failed) before this returns
     for f in writes:
         f.result()                                    # re-raises the first exception of a write, in file order
+    if mask_folder is not None:
+        with open(os.path.join(output_folder, "scores.csv"), "w") as f:
+            f.write(metrics.csv_header("image", number_classes) + "\n")
+            f.writelines(r + "\n" for r in score_rows + [metrics.csv_row("total", metrics.summarize(total))])
+        np.save(os.path.join(output_folder, "confusion.npy"), total)
 
 
 def main(argv=None):
@@ -312,9 +391,14 @@ def main(argv=None):
                     help="opt-in extra: bf16 = mixed-precision contractions (fp32 is the reference's arithmetic and the default)")
     ap.add_argument("--host_pipeline", dest="host_pipeline", action="store_true",
                     help="cut, normalise, argmax and paste every tile on the host (the reference's loop) instead of on the device; same masks")
+    ap.add_argument("--mask_folder", dest="mask_folder", type=str, default=None,
+                    help="opt-in extra: ground-truth masks (same file names as the images); also writes scores.csv (per-image and total "
+                         "pixel accuracy, mean IoU, per-class IoU and Dice) and confusion.npy into the output folder")
+    ap.add_argument("--ignore_label", dest="ignore_label", type=int, default=-1,
+                    help="with --mask_folder: ground-truth label whose pixels are not scored (-1: score every pixel)")
     a = ap.parse_args(argv)
     inference(a.checkpoint_filepath, a.image_folder, a.output_folder, a.number_classes, a.number_channels, a.image_format,
-              compute_dtype=a.compute_dtype, host_pipeline=a.host_pipeline)
+              compute_dtype=a.compute_dtype, host_pipeline=a.host_pipeline, mask_folder=a.mask_folder, ignore_label=a.ignore_label)
 
 
 if __name__ == "__main__":

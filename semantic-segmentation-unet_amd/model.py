@@ -193,13 +193,14 @@ class UNet:
         return radius
 
     # -- reference UNet/model.py:204-228
-    def train_step(self, inputs, dropout_masks=None):
+    def train_step(self, inputs, dropout_masks=None, confusion=None):
+        """confusion (metrics.ConfusionMatrix, opt-in): the step's per-class counts are added to it on the device, no host sync"""
         (images, labels, loss_metric, accuracy_metric) = inputs
         e = self.engine
         images = torch.as_tensor(np.asarray(images, dtype=np.float32)) if not torch.is_tensor(images) else images
         labels = torch.as_tensor(np.asarray(labels, dtype=np.int32)) if not torch.is_tensor(labels) else labels
         e.forward(images, training=True, dropout_masks=dropout_masks, labels=labels,
-                  global_batch_size=self.global_batch_size, label_smoothing=self.label_smoothing, want_grad=True)
+                  global_batch_size=self.global_batch_size, label_smoothing=self.label_smoothing, want_grad=True, confusion=confusion)
         if self.parallel is not None:
             self.parallel.begin_step()
         e.backward()
@@ -209,13 +210,13 @@ class UNet:
         return self._update_metrics(images, loss_metric, accuracy_metric)
 
     # -- reference UNet/model.py:237-250
-    def test_step(self, inputs):
+    def test_step(self, inputs, confusion=None):
         (images, labels, loss_metric, accuracy_metric) = inputs
         e = self.engine
         images = torch.as_tensor(np.asarray(images, dtype=np.float32)) if not torch.is_tensor(images) else images
         labels = torch.as_tensor(np.asarray(labels, dtype=np.int32)) if not torch.is_tensor(labels) else labels
         e.forward(images, training=False, labels=labels, global_batch_size=self.global_batch_size,
-                  label_smoothing=self.label_smoothing)
+                  label_smoothing=self.label_smoothing, confusion=confusion)
         return self._update_metrics(images, loss_metric, accuracy_metric)
 
     def _update_metrics(self, images, loss_metric, accuracy_metric):
@@ -238,12 +239,12 @@ class UNet:
 
     # -- reference UNet/model.py:230-235,252-256: one replica per process here; the cross-replica SUM of the per-replica
     #    losses is an RCCL all-reduce in parallel.DataParallel (reference: dist_strategy.reduce(SUM, ...)).
-    def dist_train_step(self, dist_strategy, inputs, dropout_masks=None):
-        loss = self.train_step(inputs, dropout_masks=dropout_masks)
+    def dist_train_step(self, dist_strategy, inputs, dropout_masks=None, confusion=None):
+        loss = self.train_step(inputs, dropout_masks=dropout_masks, confusion=confusion)
         return self._reduce_loss(dist_strategy, loss)
 
-    def dist_test_step(self, dist_strategy, inputs):
-        loss = self.test_step(inputs)
+    def dist_test_step(self, dist_strategy, inputs, confusion=None):
+        loss = self.test_step(inputs, confusion=confusion)
         return self._reduce_loss(dist_strategy, loss)
 
     def _reduce_loss(self, dist_strategy, loss):

@@ -56,10 +56,16 @@ def best_epoch_index(test_loss):
 
 def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, test_lmdb_filepath, use_augmentation,
                 number_classes, balance_classes, learning_rate, test_every_n_steps, early_stopping_count,
-                train_reader=None, test_reader=None, max_epochs=None, quiet=False, compute_dtype=None, unet_factory=None):
+                train_reader=None, test_reader=None, max_epochs=None, quiet=False, compute_dtype=None, unet_factory=None,
+                class_metrics=False):
     """unet_factory (tests): callable(number_classes, global_batch_size, number_channels, learning_rate, device=..., compute_dtype=...)
     standing in for model.UNet, so the loop semantics can be checked without a GPU; the default is the HIP-backed class, which
-    refuses to run anywhere but on an MI355X."""
+    refuses to run anywhere but on an MI355X.
+
+    class_metrics (opt-in extra): every test epoch accumulates one confusion matrix on the device (metrics.ConfusionMatrix, passed to
+    dist_test_step as `confusion=`; no host sync per step), reads it once summed over the replicas, prints mean / per-class IoU behind the
+    reference's own line, logs the scalars `mean_iou` and `iou_class_<k>` and rewrites `test_class_metrics.csv` (one row per epoch:
+    epoch, pixel_accuracy, mean_iou, iou_0.., dice_0..).  Early stopping and checkpointing stay on the test loss."""
     say = (lambda *a: None) if quiet else print
     for k, v in (("batch_size", batch_size), ("number_classes", number_classes), ("learning_rate", learning_rate),
                  ("test_every_n_steps", test_every_n_steps), ("balance_classes", balance_classes),
@@ -145,6 +151,11 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
         train_epoch_size = test_every_n_steps
         test_epoch_size = test_reader.get_image_count() / batch_size
         test_loss = []
+        test_confusion, class_rows, step_kw = None, [], {}
+        if class_metrics:
+            from . import metrics
+            test_confusion = metrics.ConfusionMatrix(number_classes, device=dev_, name="test_confusion")
+            step_kw = {"confusion": test_confusion}        # only with the flag on: a stand-in network need not know the keyword
         train_loss_metric, train_acc_metric = unet_model_module.Mean("train_loss"), unet_model_module.CategoricalAccuracy("train_accuracy")
         test_loss_metric, test_acc_metric = unet_model_module.Mean("test_loss"), unet_model_module.CategoricalAccuracy("test_accuracy")
         stamp = datetime.datetime.now().strftime("%Y%m%dT%H%M%S")
@@ -196,7 +207,7 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
             while step <= test_epoch_size:
                 images, labels = next(test_batches)
                 loss_value = net.dist_test_step(strategy, (images.to(dev_, non_blocking=True), labels.to(dev_, non_blocking=True),
-                                                           test_loss_metric, test_acc_metric))
+                                                           test_loss_metric, test_acc_metric), **step_kw)
                 epoch_test_loss.append(loss_value.numpy())
                 step += 1
             test_loss.append(np.mean(epoch_test_loss))             # (kept as numpy's fp32 scalar: test_loss.csv then carries the reference's text, UNet/train.py:162,173-176)
@@ -206,9 +217,23 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
                 writers[1].scalar("loss", test_loss_metric.result(), (epoch + 1) * train_epoch_size)
                 writers[1].scalar("accuracy", test_acc_metric.result(), (epoch + 1) * train_epoch_size)
             test_loss_metric.reset_states(); test_acc_metric.reset_states()
+            if test_confusion is not None:
+                cls = test_confusion.summary(strategy)             # the epoch's one read: an all-reduce over the replicas, one download
+                test_confusion.reset_states()
+                if rank == 0:
+                    say("Test Epoch: {}: mean IoU = {} IoU per class = {}".format(epoch, cls["mean_iou"], [float(v) for v in cls["iou"]]))
+                if writers:
+                    writers[1].scalar("mean_iou", cls["mean_iou"], (epoch + 1) * train_epoch_size)
+                    for k, v in enumerate(cls["iou"]):
+                        writers[1].scalar("iou_class_%d" % k, v, (epoch + 1) * train_epoch_size)
+                class_rows.append(metrics.csv_row(epoch, cls))
             if rank == 0:
                 with open(os.path.join(output_folder, "test_loss.csv"), "w") as f:
                     f.writelines(str(v) + "\n" for v in test_loss)
+                if test_confusion is not None:
+                    with open(os.path.join(output_folder, "test_class_metrics.csv"), "w") as f:
+                        f.write(metrics.csv_header("epoch", number_classes) + "\n")
+                        f.writelines(r + "\n" for r in class_rows)
             say("Epoch took: {} s".format(time.time() - t0))
             if (len(test_loss) - 1) == int(np.argmin(test_loss)):
                 say("Test loss improved: {}, saving checkpoint".format(np.min(test_loss)))
@@ -251,6 +276,9 @@ def main(argv=None):
     ap.add_argument("--compute_dtype", choices=["fp32", "bf16"], default=None,
                     help="bf16: mixed precision (the policy the reference keeps commented out, UNet/train.py:52-54): bf16 "
                          "contractions in the wide 3x3 layers, fp32 accumulation and master weights")
+    ap.add_argument("--class_metrics", dest="class_metrics", action="store_true",
+                    help="per test epoch: confusion matrix on the device -> mean / per-class IoU printed, logged and written to "
+                         "test_class_metrics.csv (pixel accuracy alone says little on masks with a few percent of foreground)")
     a = ap.parse_args(argv)
     tr = te = None
     if a.synthetic:
@@ -263,7 +291,8 @@ def main(argv=None):
         ap.error("--train_database and --test_database are required unless --synthetic is given")
     train_model(a.output_folder, a.batch_size, a.reader_count, a.train_database_filepath, a.test_database_filepath,
                 a.use_augmentation, a.number_classes, a.balance_classes, a.learning_rate, a.test_every_n_steps,
-                a.early_stopping_count, train_reader=tr, test_reader=te, max_epochs=a.max_epochs, compute_dtype=a.compute_dtype)
+                a.early_stopping_count, train_reader=tr, test_reader=te, max_epochs=a.max_epochs, compute_dtype=a.compute_dtype,
+                class_metrics=a.class_metrics)
 
 
 if __name__ == "__main__":
