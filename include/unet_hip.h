@@ -30,6 +30,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes; a loader must refuse a library whose unet_hip_abi_version() differs
  * (9: + unet_convT2x2_dgrad_x6_sums (the BF16x6 transposed-conv data gradient leaves the producer layer's BatchNorm-backward sums); added under 9 without a
  *  bump, because no existing signature changed and a loader binds by name: unet_confusion_scores, unet_confusion_masks (per-class metrics);
+ *  unet_softmax_ce_weighted(_workspace), unet_labels_onehot_ignore, unet_confusion_scores_valid (weighted loss, unlabeled pixels);
  *  8: round 6 -- + unet_bn_finalize_apply_any (statistics finalize merged into the apply launch); the bf16 3x3 kernels start their accumulators at the bias;
  *  7: round 5 -- no signature changed, but the operand unet_winograd_weight_transform_x6 / _fold_x6 write is laid out for the round-5 kernel
  *  (MFMA A-operand order per 64-channel tile, chunk and point row): an operand and the conv entry point that reads it must come from one library;
@@ -330,6 +331,25 @@ size_t unet_softmax_ce_workspace(long P);
 int unet_softmax_ce(const float* logits, int ldz, const int* labels_onehot, float* prob, float* dlogits, int lddz,
                     long P, int K, float label_smoothing, float loss_scale, float grad_scale, float ce_clip_eps,
                     float* loss_out, float* correct_out, void* ws, size_t ws_bytes, void* stream);
+/* The same loss with a weight per pixel and unlabeled pixels (csrc/loss.hip; Keras: loss_fn(labels, softmax, sample_weight=w), UNet/model.py:211).
+ * With t_p = first maximum of pixel p's one-hot row (the loop of unet_softmax_ce) and l_p = that entry point's per-pixel cross-entropy (label
+ * smoothing and the clip path included):
+ *       w_p = class_weight[t_p] * pixel_weight[p]      (fp32 [K] / [P]; a NULL pointer is a factor 1; one fp32 multiply)
+ *       loss = loss_scale * sum_p w_p * l_p,   dlogits[p][k] = (the value unet_softmax_ce stores, grad_scale included) * w_p
+ * The reduction is NOT divided by the weight sum (every replica of a data-parallel step keeps scaling by the global constant); the sum is
+ * reported.  Weights must be finite and >= 0 (checked by the host wrappers, not here).  With all weights 1 prob and dlogits are bit-identical
+ * to unet_softmax_ce.
+ * ignore_empty != 0: a pixel whose one-hot row has no positive entry is UNLABELED -- nothing added to the loss (also under label smoothing),
+ *       its dlogits row stored as +0.0 (written, not skipped), not counted in correct or valid; its prob row is still written.
+ *       ignore_empty == 0: such a row is class 0 for accuracy and for the class-weight index, as in unet_softmax_ce.
+ * stats_out (may be NULL) = [loss, correct, valid, weight_sum]: valid = pixels not ignored, weight_sum = sum of w_p over them; accumulated as
+ *       double / 64-bit integers / double in a fixed order (no floating-point atomics), stored as floats: the counts are exact below 2^24, the
+ *       convention of correct_out.  labels_onehot, prob, dlogits may be NULL as in unet_softmax_ce; class_weight, pixel_weight, ignore_empty and
+ *       stats_out need labels_onehot.  ws: 8-byte aligned, unet_softmax_ce_weighted_workspace(P) bytes. */
+size_t unet_softmax_ce_weighted_workspace(long P);
+int unet_softmax_ce_weighted(const float* logits, int ldz, const int* labels_onehot, const float* class_weight, const float* pixel_weight,
+                             int ignore_empty, float* prob, float* dlogits, int lddz, long P, int K, float label_smoothing, float loss_scale,
+                             float grad_scale, float ce_clip_eps, float* stats_out, void* ws, size_t ws_bytes, void* stream);
 /* np.argmax(softmax, axis=-1), UNet/inference.py:107,166 (first maximum wins) */
 int unet_argmax(const float* p, int ldp, int* out, long P, int K, void* stream);
 
@@ -362,6 +382,9 @@ int unet_argmax_paste(const float* prob, int ldp, int th, int tw, int K, int oy,
  *       a pixel whose truth is negative or >= K, or whose prediction is not in [0, K), is left out of cm and counted in *out_of_range (one
  *       unsigned 64-bit word, 8-byte aligned, may be NULL, else zeroed by the caller: the convention of unet_labels_onehot). */
 int unet_confusion_scores(const float* scores, int lds, const int* labels_onehot, long P, int K, void* cm, void* stream);
+/* confusion_scores with unlabeled pixels (no positive entry in the one-hot row) skipped: trace(cm) == stats_out[1] and sum(cm) == stats_out[2]
+ * of unet_softmax_ce_weighted(ignore_empty = 1) on the same logits and labels, exactly */
+int unet_confusion_scores_valid(const float* scores, int lds, const int* labels_onehot, long P, int K, void* cm, void* stream);
 int unet_confusion_masks(const void* pred, int pred_elem, long pred_pitch, const void* truth, int truth_elem, long truth_pitch,
                          int H, int W, int K, int ignore_label, void* cm, void* out_of_range, void* stream);
 
@@ -403,6 +426,9 @@ int unet_zscore_nhwc_to_nchw(const float* img, float* out, int N, int H, int W, 
  * so the feed ships 1 byte per pixel instead of 4K; *out_of_range (may be NULL, else zeroed by the caller) counts labels >= K,
  * the condition the reference raises IndexError for */
 int unet_labels_onehot(const uint8_t* classmap, int* onehot, long P, int K, unsigned* out_of_range, void* stream);
+/* the same with one class-map value that means "unlabeled": classmap == ignore_label (below or above K) writes an all-zero row and is NOT
+ * counted in *out_of_range; ignore_label = -1 ignores nothing and is bit-identical to unet_labels_onehot */
+int unet_labels_onehot_ignore(const uint8_t* classmap, int* onehot, long P, int K, int ignore_label, unsigned* out_of_range, void* stream);
 
 /* ---- workgroup-capped forms of every kernel whose grid is sized by the CU count ------------------------------------------------------
  * The reference's data-parallel step (tf.distribute.MirroredStrategy, UNet/train.py:57-61; the gradient all-reduce inside

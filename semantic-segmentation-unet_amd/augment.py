@@ -133,8 +133,14 @@ class AugmentingFeed:
     one-hot: the reference's reader order (augment, then zscore_normalize, then one-hot: UNet/imagereader.py:283-312), all on
     the device.  Yields what the train step takes: images [B,C,H,W] fp32 z-scored, labels int32 one-hot [B,H,W,K]."""
 
-    def __init__(self, feed, augmenter, number_classes):
+    def __init__(self, feed, augmenter, number_classes, ignore_label=None):
+        """ignore_label: the class-map value that means "unlabeled" (an all-zero one-hot row, unet_labels_onehot_ignore).  The mask warp is a
+        ROUNDED BILINEAR interpolation, as the reference's: next to a warped edge it can turn an ignore value into class ids in between, so
+        use this only with an augmenter that leaves the mask's values alone (train.py refuses the combination)."""
+        if ignore_label is not None and not 0 <= int(ignore_label) <= 255:
+            raise ValueError("ignore_label must be in [0, 255]")
         self.feed, self.aug, self.k = feed, augmenter, number_classes
+        self.ignore_label = None if ignore_label is None else int(ignore_label)
         self.L = augmenter.L
 
     def __iter__(self):
@@ -156,7 +162,10 @@ class AugmentingFeed:
         # class ids >= number_classes are counted on the device (the reference's reader raises IndexError for them,
         # UNet/imagereader.py:302-312); train.py reads the counter at its per-epoch sync point
         bad = getattr(self.feed, "_bad", None)
-        self.L.unet_labels_onehot(_p(cm), _p(onehot), b * h * w, self.k, _p(bad) if bad is not None else None, st)
+        if self.ignore_label is None:
+            self.L.unet_labels_onehot(_p(cm), _p(onehot), b * h * w, self.k, _p(bad) if bad is not None else None, st)
+        else:
+            self.L.unet_labels_onehot_ignore(_p(cm), _p(onehot), b * h * w, self.k, self.ignore_label, _p(bad) if bad is not None else None, st)
         return out, onehot
 
     def out_of_range_labels(self):

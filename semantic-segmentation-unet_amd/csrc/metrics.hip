@@ -1,6 +1,8 @@
 // Per-class segmentation metrics on the device: the K x K confusion matrix cm[truth][prediction] (unsigned 64-bit counts) that per-class
 // IoU / Dice / precision / recall are derived from on the host (metrics.py).  Two producers, both ACCUMULATING into the caller's matrix:
 //   unet_confusion_scores  class scores [P][lds] + one-hot labels [P][K] (the eval / train step: logits and labels are on the device)
+//   unet_confusion_scores_valid  the same with unlabeled pixels (no positive entry in the one-hot row) counted nowhere: the pair of
+//                          unet_softmax_ce_weighted(ignore_empty) (loss.hip), trace = its `correct`, sum = its `valid`
 //   unet_confusion_masks   predicted class map against a ground-truth class map (whole-image inference: the mask before its download)
 // The prediction is the FIRST maximum of the scores (start at class 0, replace on v > m: softmax_ce_kernel / argmax_kernel of misc.hip), the
 // truth the first maximum of the one-hot row by the loop of softmax_ce_kernel, so trace(cm) is exactly the `correct_out` of unet_softmax_ce
@@ -55,8 +57,16 @@ __device__ __forceinline__ void flush_wave_counts(const unsigned (&cnt)[NC], uns
 }
 
 // ---- scores, K <= 4.  PPT pixels per thread; DENSE: lds == K and both pointers aligned to PPT * K * 4 bytes, so a thread's PPT * K scores
-// (and labels) are one 8- or 16-byte load.
-template <int K, int PPT, int DENSE>
+// (and labels) are one 8- or 16-byte load.  VALID (unet_confusion_scores_valid): a pixel whose one-hot row has no positive entry is unlabeled
+// and counted nowhere.
+template <int K> __device__ __forceinline__ bool any_positive(const int* v) {
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < K; ++k) any |= v[k] > 0;
+    return any;
+}
+
+template <int K, int PPT, int DENSE, int VALID>
 __global__ __launch_bounds__(WG) void confusion_scores_ballot_kernel(const float* __restrict__ z, int ldz, const int* __restrict__ lab, long P,
                                                                      u64* __restrict__ cm) {
     constexpr int KK = K * K, NV = PPT * K;
@@ -99,7 +109,8 @@ __global__ __launch_bounds__(WG) void confusion_scores_ballot_kernel(const float
                 }
             }
 #pragma unroll
-            for (int j = 0; j < PPT; ++j) if (j < np) cell[j] = first_max<K>(l + j * K) * K + first_max<K>(s + j * K);
+            for (int j = 0; j < PPT; ++j)
+                if (j < np && (VALID == 0 || any_positive<K>(l + j * K))) cell[j] = first_max<K>(l + j * K) * K + first_max<K>(s + j * K);
         }
 #pragma unroll
         for (int j = 0; j < PPT; ++j) {
@@ -112,7 +123,7 @@ __global__ __launch_bounds__(WG) void confusion_scores_ballot_kernel(const float
 
 // ---- scores, K > 4: LDS histogram (use_lds, K <= 64) or global atomics
 __global__ __launch_bounds__(WG) void confusion_scores_hist_kernel(const float* __restrict__ z, int ldz, const int* __restrict__ lab, long P, int K,
-                                                                   u64* __restrict__ cm, int use_lds) {
+                                                                   u64* __restrict__ cm, int use_lds, int skip_empty) {
     extern __shared__ unsigned hist[];
     const int KK = K * K;
     if (use_lds) {
@@ -127,6 +138,7 @@ __global__ __launch_bounds__(WG) void confusion_scores_hist_kernel(const float* 
         const int* lp = lab + (size_t)pix * K;
         int lbest = lp[0], al = 0;
         for (int k = 1; k < K; ++k) { const int li = lp[k]; if (li > lbest) { lbest = li; al = k; } }
+        if (skip_empty && lbest <= 0) continue;
         const int cell = al * K + am;
         if (use_lds) atomicAdd(&hist[cell], 1u);
         else atomicAdd(cm + cell, (u64)1);
@@ -240,45 +252,55 @@ int grid_counting(long items, long pixels) {
 
 bool aligned_to(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1u)) == 0; }
 
-template <int K>
+template <int K, int VALID>
 int launch_scores_ballot(const float* z, int ldz, const int* lab, long P, u64* cm, hipStream_t st) {
     if constexpr (K == 2) {
         if (ldz == 2 && aligned_to(z, 16) && aligned_to(lab, 16) && P >= 2) {
-            confusion_scores_ballot_kernel<2, 2, 1><<<grid_counting((P + 1) / 2, P), WG, 0, st>>>(z, ldz, lab, P, cm);
+            confusion_scores_ballot_kernel<2, 2, 1, VALID><<<grid_counting((P + 1) / 2, P), WG, 0, st>>>(z, ldz, lab, P, cm);
             return UNET_LAUNCH_STATUS();
         }
         if (ldz == 2 && aligned_to(z, 8) && aligned_to(lab, 8)) {
-            confusion_scores_ballot_kernel<2, 1, 1><<<grid_counting(P, P), WG, 0, st>>>(z, ldz, lab, P, cm);
+            confusion_scores_ballot_kernel<2, 1, 1, VALID><<<grid_counting(P, P), WG, 0, st>>>(z, ldz, lab, P, cm);
             return UNET_LAUNCH_STATUS();
         }
     }
     if constexpr (K == 4) {
         if (ldz == 4 && aligned_to(z, 16) && aligned_to(lab, 16)) {
-            confusion_scores_ballot_kernel<4, 1, 1><<<grid_counting(P, P), WG, 0, st>>>(z, ldz, lab, P, cm);
+            confusion_scores_ballot_kernel<4, 1, 1, VALID><<<grid_counting(P, P), WG, 0, st>>>(z, ldz, lab, P, cm);
             return UNET_LAUNCH_STATUS();
         }
     }
-    confusion_scores_ballot_kernel<K, 1, 0><<<grid_counting(P, P), WG, 0, st>>>(z, ldz, lab, P, cm);
+    confusion_scores_ballot_kernel<K, 1, 0, VALID><<<grid_counting(P, P), WG, 0, st>>>(z, ldz, lab, P, cm);
+    return UNET_LAUNCH_STATUS();
+}
+
+template <int VALID>
+int confusion_scores(const float* scores, int lds, const int* labels_onehot, long P, int K, void* cmv, void* stream) {
+    UNET_CHECK_ARG(scores && labels_onehot && cmv && P > 0 && K >= 1 && K <= 1024 && lds >= K);
+    UNET_CHECK_ARG(aligned_to(scores, 4) && aligned_to(labels_onehot, 4) && aligned_to(cmv, 8));
+    u64* cm = (u64*)cmv;
+    hipStream_t st = (hipStream_t)stream;
+    switch (K) {
+        case 1: return launch_scores_ballot<1, VALID>(scores, lds, labels_onehot, P, cm, st);
+        case 2: return launch_scores_ballot<2, VALID>(scores, lds, labels_onehot, P, cm, st);
+        case 3: return launch_scores_ballot<3, VALID>(scores, lds, labels_onehot, P, cm, st);
+        case 4: return launch_scores_ballot<4, VALID>(scores, lds, labels_onehot, P, cm, st);
+        default: break;
+    }
+    const int use_lds = K <= 64;
+    confusion_scores_hist_kernel<<<grid_counting(P, P), WG, use_lds ? (size_t)K * K * 4 : 0, st>>>(scores, lds, labels_onehot, P, K, cm, use_lds, VALID);
     return UNET_LAUNCH_STATUS();
 }
 
 }  // namespace
 
 extern "C" int unet_confusion_scores(const float* scores, int lds, const int* labels_onehot, long P, int K, void* cmv, void* stream) {
-    UNET_CHECK_ARG(scores && labels_onehot && cmv && P > 0 && K >= 1 && K <= 1024 && lds >= K);
-    UNET_CHECK_ARG(aligned_to(scores, 4) && aligned_to(labels_onehot, 4) && aligned_to(cmv, 8));
-    u64* cm = (u64*)cmv;
-    hipStream_t st = (hipStream_t)stream;
-    switch (K) {
-        case 1: return launch_scores_ballot<1>(scores, lds, labels_onehot, P, cm, st);
-        case 2: return launch_scores_ballot<2>(scores, lds, labels_onehot, P, cm, st);
-        case 3: return launch_scores_ballot<3>(scores, lds, labels_onehot, P, cm, st);
-        case 4: return launch_scores_ballot<4>(scores, lds, labels_onehot, P, cm, st);
-        default: break;
-    }
-    const int use_lds = K <= 64;
-    confusion_scores_hist_kernel<<<grid_counting(P, P), WG, use_lds ? (size_t)K * K * 4 : 0, st>>>(scores, lds, labels_onehot, P, K, cm, use_lds);
-    return UNET_LAUNCH_STATUS();
+    return confusion_scores<0>(scores, lds, labels_onehot, P, K, cmv, stream);
+}
+
+// the same counting with unlabeled pixels (no positive entry in the one-hot row) skipped: the pair of unet_softmax_ce_weighted(ignore_empty)
+extern "C" int unet_confusion_scores_valid(const float* scores, int lds, const int* labels_onehot, long P, int K, void* cmv, void* stream) {
+    return confusion_scores<1>(scores, lds, labels_onehot, P, K, cmv, stream);
 }
 
 extern "C" int unet_confusion_masks(const void* pred, int pred_elem, long pred_pitch, const void* truth, int truth_elem, long truth_pitch,

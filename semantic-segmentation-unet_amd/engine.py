@@ -111,6 +111,8 @@ class Engine:
         self.bufs = {}
         self._ws = None
         self.loss_buf = torch.zeros(2, dtype=torch.float32, device=self.dev)             # [loss, correct]
+        self.loss_stats = torch.zeros(4, dtype=torch.float32, device=self.dev)           # weighted loss: [loss, correct, valid, weight_sum]
+        self.weighted_loss = False              # the last forward with labels took unet_softmax_ce_weighted (loss_stats is current)
         self.dropout_seed = seed
         self.ce_clip_eps = CE_CLIP_EPS
         self._eval_folded = set()               # layers whose eval-mode (moving-statistics) BatchNorm-on-load fold is current
@@ -542,12 +544,16 @@ class Engine:
         return out
 
     def forward(self, images, training=False, dropout_masks=None, labels=None, global_batch_size=None,
-                label_smoothing=0.0, want_grad=False, confusion=None):
+                label_smoothing=0.0, want_grad=False, confusion=None, class_weights=None, pixel_weights=None, ignore_unlabeled=False):
         """images: fp32 [N,C,H,W] (reference input contract, UNet/imagereader.py:298-300).  Returns softmax [N,H,W,K]
         (a device tensor owned by the engine; valid until the next call).  With labels (int32 one-hot [N,H,W,K]) the
         loss and the count of correctly classified pixels land in self.loss_buf.  confusion (metrics.ConfusionMatrix, needs labels): the
         step's K x K counts are added to it by one more launch behind the loss kernel, on the same stream, from the LOGITS and the labels the
-        step already holds (its trace is the count in loss_buf[1]); None = not one extra launch."""
+        step already holds (its trace is the count in loss_buf[1]); None = not one extra launch.
+        class_weights (fp32 [K] device tensor), pixel_weights (fp32 [N,H,W] device tensor), ignore_unlabeled: the weighted loss
+        (unet_softmax_ce_weighted: w_p = class_weights[truth] * pixel_weights[p], all-zero one-hot rows left out); [loss, correct, valid,
+        weight_sum] land in self.loss_stats, the first two in loss_buf as well.  Values are the caller's to validate (model.UNet does).  With
+        all three unset the launch is unet_softmax_ce, as ever."""
         if confusion is not None and labels is None:
             raise ValueError("a confusion matrix needs labels")
         L, st = self.L, self._stream()
@@ -651,12 +657,28 @@ class Engine:
             G = global_batch_size if global_batch_size else n
             scale = 1.0 / (float(G) * h * w)                       # sum_n / G then mean over H,W  (UNet/model.py:213-215)
             dl = self._buf("dy_logits", (n, h, w, self.K)) if want_grad else None
-            self._timed("softmax_ce", self._nb(yl, lab, prob, dl), L.unet_softmax_ce,
-                        _p(yl), self.K, _p(lab), _p(prob), _p(dl), self.K, P, self.K, float(label_smoothing), scale,
-                        scale, float(self.ce_clip_eps), _p(self.loss_buf[0:1]), _p(self.loss_buf[1:2]), _p(ws), nb, st)
+            self.weighted_loss = class_weights is not None or pixel_weights is not None or bool(ignore_unlabeled)
+            if not self.weighted_loss:
+                self._timed("softmax_ce", self._nb(yl, lab, prob, dl), L.unet_softmax_ce,
+                            _p(yl), self.K, _p(lab), _p(prob), _p(dl), self.K, P, self.K, float(label_smoothing), scale,
+                            scale, float(self.ce_clip_eps), _p(self.loss_buf[0:1]), _p(self.loss_buf[1:2]), _p(ws), nb, st)
+            else:
+                cw, pw = class_weights, pixel_weights
+                for t, shape, what in ((cw, (self.K,), "class_weights"), (pw, (n, h, w), "pixel_weights")):
+                    if t is not None and not (torch.is_tensor(t) and t.device == prob.device and t.dtype == torch.float32
+                                              and tuple(t.shape) == shape and t.is_contiguous()):
+                        raise ValueError("%s must be a contiguous fp32 tensor %s on %s" % (what, list(shape), prob.device))
+                nbw = L.unet_softmax_ce_weighted_workspace(P)
+                ws = self._workspace(nbw)
+                self._timed("softmax_ce_weighted", self._nb(yl, lab, prob, dl, pw), L.unet_softmax_ce_weighted,
+                            _p(yl), self.K, _p(lab), _p(cw), _p(pw), int(bool(ignore_unlabeled)), _p(prob), _p(dl), self.K, P, self.K,
+                            float(label_smoothing), scale, scale, float(self.ce_clip_eps), _p(self.loss_stats), _p(ws), nbw, st)
+                self.loss_buf.copy_(self.loss_stats[:2])
+                self._weights_keepalive = (cw, pw)
             self._labels_keepalive = lab
             if confusion is not None:
-                self._timed("confusion", self._nb(yl, lab), confusion.update_from_scores, yl, lab, st)
+                self._timed("confusion", self._nb(yl, lab), confusion.update_from_scores, yl, lab, st,
+                            *((True,) if ignore_unlabeled else ()))
         return prob
 
     # ------------------------------------------------------------------------------------------------ backward

@@ -12,6 +12,8 @@ runs.  This is that stage for the HIP engine:
   * label transport: either the reader's int32 one-hot [B,H,W,K] (the reference's contract, UNet/imagereader.py:302-312),
     or - `classmap=True` - the uint8 class map [B,H,W], expanded to the same one-hot on the device by
     `unet_labels_onehot` (4K x fewer bytes over PCIe, and no host-side one-hot); both give bit-identical device tensors.
+    With `ignore_label=L` (classmap feeds) a class-map value L means "unlabeled": its one-hot row is all zero and it is not
+    counted as out of range (`unet_labels_onehot_ignore`); model.UNet(ignore_unlabeled=True) trains past such pixels.
 
 `batches` may be a LIST of iterators (e.g. one seeded reader per worker, like the reference's `reader_count` processes,
 UNet/imagereader.py:182-186): each gets its own staging thread - tensor ops release the GIL - and batches are handed out in
@@ -27,12 +29,15 @@ import torch
 
 
 class DeviceFeed:
-    def __init__(self, batches, device, depth=3, classmap=False, number_classes=None, onehot=True):
+    def __init__(self, batches, device, depth=3, classmap=False, number_classes=None, onehot=True, ignore_label=None):
         assert depth >= 2
         self.dev = torch.device(device)
         self.cuda = self.dev.type == "cuda"
         self.depth, self.classmap, self.k = depth, classmap, number_classes
         self.onehot = onehot                      # False (classmap feeds only): hand out the uint8 class map itself
+        if ignore_label is not None and not (classmap and 0 <= int(ignore_label) <= 255):
+            raise ValueError("ignore_label needs a classmap feed and a value in [0, 255]")
+        self.ignore_label = None if ignore_label is None else int(ignore_label)
         if classmap:
             assert number_classes is not None and 0 < number_classes <= 256
         self._its = [iter(b) for b in batches] if isinstance(batches, (list, tuple)) else [iter(batches)]
@@ -107,9 +112,12 @@ class DeviceFeed:
                         sl["dev_lab"].copy_(sl["pin_lab"], non_blocking=True)
                         if self.classmap and self.onehot:
                             n = sl["dev_lab"].numel()
-                            self._L.unet_labels_onehot(ctypes.c_void_p(sl["dev_lab"].data_ptr()), ctypes.c_void_p(sl["dev_onehot"].data_ptr()),
-                                                       n, self.k, ctypes.c_void_p(self._bad.data_ptr()),
-                                                       ctypes.c_void_p(self._copy.cuda_stream))
+                            args = (ctypes.c_void_p(sl["dev_lab"].data_ptr()), ctypes.c_void_p(sl["dev_onehot"].data_ptr()), n, self.k)
+                            tail = (ctypes.c_void_p(self._bad.data_ptr()), ctypes.c_void_p(self._copy.cuda_stream))
+                            if self.ignore_label is None:
+                                self._L.unet_labels_onehot(*args, *tail)
+                            else:
+                                self._L.unet_labels_onehot_ignore(*args, self.ignore_label, *tail)
                         sl["ready"].record(self._copy)
                 self._ready.put(s)
         except BaseException as e:                # surfaced on the consumer side
@@ -137,9 +145,12 @@ class DeviceFeed:
         if not self.cuda:
             lab = sl["pin_lab"]
             if self.classmap and self.onehot:
-                if int(lab.max()) >= self.k:
+                cls = lab.long()
+                unl = cls == self.ignore_label if self.ignore_label is not None else torch.zeros_like(cls, dtype=torch.bool)
+                if int(cls.masked_fill(unl, 0).max()) >= self.k:
                     raise IndexError("Number of classes specified differs from number of observed classes in data")
-                lab = torch.nn.functional.one_hot(lab.long(), self.k).to(torch.int32)
+                lab = torch.nn.functional.one_hot(cls.masked_fill(unl, 0), self.k).to(torch.int32)
+                lab[unl] = 0
             return sl["pin_img"].clone(), lab.clone()
         torch.cuda.current_stream(self.dev).wait_event(sl["ready"])
         return sl["dev_img"], (sl["dev_onehot"] if self.classmap and self.onehot else sl["dev_lab"])

@@ -49,9 +49,11 @@ class ConfusionMatrix:
             if not torch.is_tensor(t) or t.device != self.device:
                 raise ValueError("%s must be a tensor on %s (got %s)" % (name, self.device, t.device if torch.is_tensor(t) else type(t).__name__))
 
-    def update_from_scores(self, scores, labels_onehot, stream=None):
+    def update_from_scores(self, scores, labels_onehot, stream=None, ignore_unlabeled=False):
         """scores: fp32 [..., K] device tensor whose last axis may be a channel slice (stride(-2) = leading dimension) -- pass the LOGITS;
-        labels_onehot: contiguous int32 [..., K].  stream: a hipStream_t handle (None: the current torch stream)."""
+        labels_onehot: contiguous int32 [..., K].  stream: a hipStream_t handle (None: the current torch stream).  ignore_unlabeled: pixels
+        whose one-hot row has no positive entry are counted nowhere (`unet_confusion_scores_valid`): trace and sum of the added counts are
+        the `correct` and `valid` of the weighted loss with ignore_unlabeled on the same tensors, exactly."""
         L = self._lib()
         self._on_device(scores=scores, labels_onehot=labels_onehot)
         k = self.number_classes
@@ -62,7 +64,8 @@ class ConfusionMatrix:
         lds = scores.stride(-2) if scores.dim() > 1 and scores.numel() > k else k
         if stream is None:
             stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        L.unet_confusion_scores(_ptr(scores), lds, _ptr(labels_onehot), labels_onehot.numel() // k, k, _ptr(self.matrix), stream)
+        fn = L.unet_confusion_scores_valid if ignore_unlabeled else L.unet_confusion_scores
+        fn(_ptr(scores), lds, _ptr(labels_onehot), labels_onehot.numel() // k, k, _ptr(self.matrix), stream)
 
     _PRED_ELEM = {torch.uint8: 1, torch.int32: 4}
     _TRUTH_ELEM = {torch.uint8: 1, torch.int16: 2, torch.int32: 4}          # (+ torch.uint16 where this torch has it)

@@ -69,6 +69,16 @@ class _Loss:
         return float(self._t.item())
 
 
+def check_weights(values, what, shape=None):
+    """Loss weights as an fp32 numpy array: finite and >= 0 (the kernel does not check), of `shape` when given."""
+    a = np.asarray(values, dtype=np.float32)
+    if shape is not None and tuple(a.shape) != tuple(shape):
+        raise ValueError("%s must have shape %s, got %s" % (what, list(shape), list(a.shape)))
+    if not np.isfinite(a).all() or (a < 0).any():
+        raise ValueError("%s must be finite and >= 0" % what)
+    return a
+
+
 class _KerasLikeModel:
     """`unet.get_keras_model()`: callable as m(x, training=False) with x fp32 [N,C,H,W] (numpy or torch), returning the
     softmax [N,H,W,K] (reference UNet/inference.py:105,164; UNet/model.py:177,209,239)."""
@@ -109,13 +119,22 @@ class UNet:
     RADIUS = 96
 
     def __init__(self, number_classes, global_batch_size, number_channels, learning_rate=3e-4, label_smoothing=0,
-                 device="cuda", seed=0, compute_dtype=None):
+                 device="cuda", seed=0, compute_dtype=None, class_weights=None, ignore_unlabeled=False):
+        """class_weights (length number_classes, finite, >= 0), ignore_unlabeled, and the steps' pixel_weights: the weighted loss
+        loss = sum_p class_weights[truth_p] * pixel_weights[p] * ce_p / (G H W) -- Keras' sample_weight under the reference's reduction, NOT
+        divided by the weight sum; with ignore_unlabeled a pixel whose one-hot row is all zero (feed.DeviceFeed(ignore_label=...)) adds no
+        loss and no gradient and leaves the accuracy's numerator and denominator.  All unset: the reference's loss, the launches of before."""
         self.number_channels = number_channels
         self.learning_rate = learning_rate
         self.number_classes = number_classes
         self.global_batch_size = global_batch_size
         self.label_smoothing = label_smoothing
         self.engine = Engine(number_classes, number_channels, device=device, seed=seed)
+        self.ignore_unlabeled = bool(ignore_unlabeled)
+        self.class_weights = None
+        if class_weights is not None:                            # validated and uploaded once
+            cw = check_weights(class_weights, "class_weights", (number_classes,))
+            self.class_weights = torch.as_tensor(cw).to(self.engine.dev)
         if compute_dtype is not None:        # "fp32" (reference arithmetic) | "bf16" (mixed precision the reference leaves commented
             if compute_dtype not in ("fp32", "bf16"):                                  # out, UNet/train.py:52-54)
                 raise ValueError("compute_dtype must be 'fp32' or 'bf16'")
@@ -193,14 +212,38 @@ class UNet:
         return radius
 
     # -- reference UNet/model.py:204-228
-    def train_step(self, inputs, dropout_masks=None, confusion=None):
-        """confusion (metrics.ConfusionMatrix, opt-in): the step's per-class counts are added to it on the device, no host sync"""
+    def _pixel_weights(self, pixel_weights, images):
+        """[N,H,W] fp32, numpy (validated here) or device tensor (the caller's to keep finite and >= 0: no host sync) -> device tensor"""
+        if pixel_weights is None:
+            return None
+        n, _, h, w = images.shape
+        if torch.is_tensor(pixel_weights):
+            if tuple(pixel_weights.shape) != (n, h, w):
+                raise ValueError("pixel_weights must have shape %s, got %s" % ([n, h, w], list(pixel_weights.shape)))
+            return pixel_weights.to(device=self.engine.dev, dtype=torch.float32).contiguous()
+        return torch.as_tensor(check_weights(pixel_weights, "pixel_weights", (n, h, w))).to(self.engine.dev)
+
+    def _loss_kw(self, pixel_weights, images):
+        """forward()'s weighted-loss keywords; empty when nothing is set, so the default step calls forward() as it always did"""
+        kw = {}
+        if self.class_weights is not None:
+            kw["class_weights"] = self.class_weights
+        if pixel_weights is not None:
+            kw["pixel_weights"] = self._pixel_weights(pixel_weights, images)
+        if self.ignore_unlabeled:
+            kw["ignore_unlabeled"] = True
+        return kw
+
+    def train_step(self, inputs, dropout_masks=None, confusion=None, pixel_weights=None):
+        """confusion (metrics.ConfusionMatrix, opt-in): the step's per-class counts are added to it on the device, no host sync;
+        pixel_weights ([N,H,W] fp32, opt-in): the per-pixel factor of the weighted loss"""
         (images, labels, loss_metric, accuracy_metric) = inputs
         e = self.engine
         images = torch.as_tensor(np.asarray(images, dtype=np.float32)) if not torch.is_tensor(images) else images
         labels = torch.as_tensor(np.asarray(labels, dtype=np.int32)) if not torch.is_tensor(labels) else labels
         e.forward(images, training=True, dropout_masks=dropout_masks, labels=labels,
-                  global_batch_size=self.global_batch_size, label_smoothing=self.label_smoothing, want_grad=True, confusion=confusion)
+                  global_batch_size=self.global_batch_size, label_smoothing=self.label_smoothing, want_grad=True, confusion=confusion,
+                  **self._loss_kw(pixel_weights, images))
         if self.parallel is not None:
             self.parallel.begin_step()
         e.backward()
@@ -210,18 +253,20 @@ class UNet:
         return self._update_metrics(images, loss_metric, accuracy_metric)
 
     # -- reference UNet/model.py:237-250
-    def test_step(self, inputs, confusion=None):
+    def test_step(self, inputs, confusion=None, pixel_weights=None):
         (images, labels, loss_metric, accuracy_metric) = inputs
         e = self.engine
         images = torch.as_tensor(np.asarray(images, dtype=np.float32)) if not torch.is_tensor(images) else images
         labels = torch.as_tensor(np.asarray(labels, dtype=np.int32)) if not torch.is_tensor(labels) else labels
         e.forward(images, training=False, labels=labels, global_batch_size=self.global_batch_size,
-                  label_smoothing=self.label_smoothing, confusion=confusion)
+                  label_smoothing=self.label_smoothing, confusion=confusion, **self._loss_kw(pixel_weights, images))
         return self._update_metrics(images, loss_metric, accuracy_metric)
 
     def _update_metrics(self, images, loss_metric, accuracy_metric):
         e = self.engine
-        vals = e.loss_buf.clone()                                        # [per-replica loss, correctly classified pixels]
+        # [per-replica loss, correctly classified pixels]; behind the weighted loss also [labeled pixels, weight sum], which travel in the
+        # same all-reduce
+        vals = e.loss_stats.clone() if e.weighted_loss else e.loss_buf.clone()
         self._reduced = None
         if loss_metric is not None or accuracy_metric is not None:       # forces the per-step host sync the reference has
             world = 1
@@ -234,17 +279,18 @@ class UNet:
             if loss_metric is not None:
                 loss_metric.add(lb[0], world) if hasattr(loss_metric, "add") else loss_metric.update_state(lb[0] / world)
             if accuracy_metric is not None:
-                accuracy_metric.update_state(lb[1], n * h * w * world)
+                # unlabeled pixels are in neither count: the denominator is the labeled pixels summed over the replicas
+                accuracy_metric.update_state(lb[1], lb[2] if (e.weighted_loss and self.ignore_unlabeled) else n * h * w * world)
         return _Loss(vals[0:1])
 
     # -- reference UNet/model.py:230-235,252-256: one replica per process here; the cross-replica SUM of the per-replica
     #    losses is an RCCL all-reduce in parallel.DataParallel (reference: dist_strategy.reduce(SUM, ...)).
-    def dist_train_step(self, dist_strategy, inputs, dropout_masks=None, confusion=None):
-        loss = self.train_step(inputs, dropout_masks=dropout_masks, confusion=confusion)
+    def dist_train_step(self, dist_strategy, inputs, dropout_masks=None, confusion=None, pixel_weights=None):
+        loss = self.train_step(inputs, dropout_masks=dropout_masks, confusion=confusion, pixel_weights=pixel_weights)
         return self._reduce_loss(dist_strategy, loss)
 
-    def dist_test_step(self, dist_strategy, inputs, confusion=None):
-        loss = self.test_step(inputs, confusion=confusion)
+    def dist_test_step(self, dist_strategy, inputs, confusion=None, pixel_weights=None):
+        loss = self.test_step(inputs, confusion=confusion, pixel_weights=pixel_weights)
         return self._reduce_loss(dist_strategy, loss)
 
     def _reduce_loss(self, dist_strategy, loss):

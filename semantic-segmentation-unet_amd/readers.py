@@ -100,8 +100,10 @@ class TileFolderReader(_Base):
       * shuffle=False: worker `w` of `num_workers` walks keys w, w+num_workers, ... modulo the key count (:239-241) and
         class balancing is ignored ("without shuffle you cannot balance classes", :238)."""
 
-    def __init__(self, folder, number_classes, shuffle=False, seed=0, balance_classes=False):
+    def __init__(self, folder, number_classes, shuffle=False, seed=0, balance_classes=False, ignore_label=None):
+        """ignore_label: a mask value (0..255) that means "unlabeled" and is exempt from the class-range check of the class-map hand-over"""
         self.folder, self.k, self.shuffle, self.seed = folder, number_classes, shuffle, seed
+        self.ignore_label = ignore_label
         self.balance_classes = bool(balance_classes)
         self.names = sorted(f[:-4] for f in os.listdir(folder) if f.endswith(".npy") and not f.endswith("_mask.npy"))
         if not self.names:
@@ -130,7 +132,8 @@ class TileFolderReader(_Base):
         im = im[..., None] if im.ndim == 2 else im
         mk = np.load(os.path.join(self.folder, name + "_mask.npy"))
         if classmap:
-            if mk.max(initial=0) >= self.k or mk.min(initial=0) < 0:
+            seen = mk if self.ignore_label is None else mk[mk != self.ignore_label]
+            if seen.max(initial=0) >= self.k or seen.min(initial=0) < 0:
                 raise IndexError("Number of classes specified differs from number of observed classes in data")
             chw = im.transpose(2, 0, 1)
             return (np.ascontiguousarray(chw, dtype=np.float32) if raw else zscore_normalize(chw)), mk.astype(np.uint8)

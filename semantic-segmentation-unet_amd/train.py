@@ -54,10 +54,21 @@ def best_epoch_index(test_loss):
     return int(np.where(err == 0)[0][0])
 
 
+def parse_class_weights(text, number_classes):
+    """`--class_weights w0,w1,...`: one finite weight >= 0 per class."""
+    try:
+        w = [float(v) for v in str(text).split(",")]
+    except ValueError:
+        raise ValueError("--class_weights must be comma-separated numbers, got %r" % (text,))
+    if len(w) != number_classes:
+        raise ValueError("--class_weights has %d entries but --number_classes is %d" % (len(w), number_classes))
+    return [float(v) for v in unet_model_module.check_weights(w, "--class_weights")]
+
+
 def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, test_lmdb_filepath, use_augmentation,
                 number_classes, balance_classes, learning_rate, test_every_n_steps, early_stopping_count,
                 train_reader=None, test_reader=None, max_epochs=None, quiet=False, compute_dtype=None, unet_factory=None,
-                class_metrics=False):
+                class_metrics=False, class_weights=None, ignore_label=None):
     """unet_factory (tests): callable(number_classes, global_batch_size, number_channels, learning_rate, device=..., compute_dtype=...)
     standing in for model.UNet, so the loop semantics can be checked without a GPU; the default is the HIP-backed class, which
     refuses to run anywhere but on an MI355X.
@@ -65,8 +76,25 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
     class_metrics (opt-in extra): every test epoch accumulates one confusion matrix on the device (metrics.ConfusionMatrix, passed to
     dist_test_step as `confusion=`; no host sync per step), reads it once summed over the replicas, prints mean / per-class IoU behind the
     reference's own line, logs the scalars `mean_iou` and `iou_class_<k>` and rewrites `test_class_metrics.csv` (one row per epoch:
-    epoch, pixel_accuracy, mean_iou, iou_0.., dice_0..).  Early stopping and checkpointing stay on the test loss."""
+    epoch, pixel_accuracy, mean_iou, iou_0.., dice_0..).  Early stopping and checkpointing stay on the test loss.
+
+    class_weights (opt-in extra, one per class) weight every pixel's loss by its truth class; ignore_label (opt-in extra) is the mask value
+    of unlabeled pixels: the feeds turn it into an all-zero one-hot row, and the network (`ignore_unlabeled=True`), the accuracy and the
+    test-epoch confusion matrix leave such pixels out.  Both reach the network as keywords only when set."""
     say = (lambda *a: None) if quiet else print
+    # the weighted-loss options are checked before anything is opened
+    if class_weights is not None:
+        class_weights = [float(v) for v in unet_model_module.check_weights(class_weights, "class_weights", (number_classes,))]
+    if ignore_label is not None:
+        ignore_label = int(ignore_label)
+        if not 0 <= ignore_label <= 255:
+            raise ValueError("--ignore_label must be in [0, 255] (masks travel as uint8 class maps)")
+        if use_augmentation and not getattr(train_reader, "augments_itself", False):
+            raise ValueError("--ignore_label cannot be combined with --use_augmentation 1: the augmentation warps masks by rounded bilinear "
+                             "interpolation (as the reference does), which smears the ignore value into neighbouring class ids; "
+                             "pass --use_augmentation 0 (a nearest-neighbour mask warp is not implemented)")
+        if os.environ.get("UNET_FEED", "1") == "0":
+            raise ValueError("--ignore_label needs the device feed (UNET_FEED=0 hands over the reader's own one-hot labels)")
     for k, v in (("batch_size", batch_size), ("number_classes", number_classes), ("learning_rate", learning_rate),
                  ("test_every_n_steps", test_every_n_steps), ("balance_classes", balance_classes),
                  ("use_augmentation", use_augmentation), ("train_database", train_lmdb_filepath),
@@ -98,12 +126,12 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
     test_reader = readers.as_batch_reader(test_reader) if test_reader is not None else None
     if train_reader is None:
         train_reader = readers.TileFolderReader(train_lmdb_filepath, number_classes, shuffle=True, seed=0,
-                                                balance_classes=bool(balance_classes))
+                                                balance_classes=bool(balance_classes), ignore_label=ignore_label)
     elif balance_classes and not getattr(train_reader, "balance_classes", False):
         raise ValueError("--balance_classes 1 needs a reader that implements class-balanced sampling (readers.TileFolderReader); "
                          "the reader passed in does not")
     if test_reader is None:
-        test_reader = readers.TileFolderReader(test_lmdb_filepath, number_classes, shuffle=False)
+        test_reader = readers.TileFolderReader(test_lmdb_filepath, number_classes, shuffle=False, ignore_label=ignore_label)
 
     def worker_batches(reader, **kw):
         import inspect
@@ -121,6 +149,7 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
         # device feed (feed.py): reader batches are staged and copied on a copy stream while the previous step runs, labels
         # travel as uint8 class maps and become the one-hot on the device; UNET_FEED=0 restores the synchronous hand-over
         use_feed = os.environ.get("UNET_FEED", "1") != "0"
+        feed_kw = {"ignore_label": ignore_label} if ignore_label is not None else {}
         if use_feed:
             from .feed import DeviceFeed
             if use_augmentation and not getattr(train_reader, "augments_itself", False):
@@ -134,15 +163,22 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
                     scale_augmentation_severity=0.1, blur_augmentation_max_sigma=2, intensity_augmentation_severity=None,
                     seed=rank, device=dev_), number_classes)
             else:
-                train_batches = DeviceFeed(worker_batches(train_reader, classmap=True, pin=False), dev_, classmap=True, number_classes=number_classes)
-            test_batches = DeviceFeed(worker_batches(test_reader, classmap=True, pin=False), dev_, classmap=True, number_classes=number_classes)
+                train_batches = DeviceFeed(worker_batches(train_reader, classmap=True, pin=False), dev_, classmap=True, number_classes=number_classes,
+                                           **feed_kw)
+            test_batches = DeviceFeed(worker_batches(test_reader, classmap=True, pin=False), dev_, classmap=True, number_classes=number_classes,
+                                      **feed_kw)
             feeds = [train_batches, test_batches]
         else:
             train_batches = readers.round_robin(worker_batches(train_reader))
             test_batches = readers.round_robin(worker_batches(test_reader))
         number_channels = train_reader.get_image_size()[2]
+        loss_kw = {}                                        # only what is set: a stand-in network need not know the keywords
+        if class_weights is not None:
+            loss_kw["class_weights"] = class_weights
+        if ignore_label is not None:
+            loss_kw["ignore_unlabeled"] = True
         net = (unet_factory or unet_model_module.UNet)(number_classes, global_batch_size, number_channels, learning_rate,
-                                                       device=dev_, compute_dtype=compute_dtype)
+                                                       device=dev_, compute_dtype=compute_dtype, **loss_kw)
         strategy = None
         if world > 1 and unet_factory is None:
             from .parallel import DataParallel
@@ -155,6 +191,7 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
         if class_metrics:
             from . import metrics
             test_confusion = metrics.ConfusionMatrix(number_classes, device=dev_, name="test_confusion")
+            # (with ignore_label the network passes ignore_unlabeled on to update_from_scores: unlabeled pixels are in no cell)
             step_kw = {"confusion": test_confusion}        # only with the flag on: a stand-in network need not know the keyword
         train_loss_metric, train_acc_metric = unet_model_module.Mean("train_loss"), unet_model_module.CategoricalAccuracy("train_accuracy")
         test_loss_metric, test_acc_metric = unet_model_module.Mean("test_loss"), unet_model_module.CategoricalAccuracy("test_accuracy")
@@ -279,7 +316,22 @@ def main(argv=None):
     ap.add_argument("--class_metrics", dest="class_metrics", action="store_true",
                     help="per test epoch: confusion matrix on the device -> mean / per-class IoU printed, logged and written to "
                          "test_class_metrics.csv (pixel accuracy alone says little on masks with a few percent of foreground)")
+    ap.add_argument("--class_weights", dest="class_weights", type=str, default=None,
+                    help="w0,w1,...: one loss weight per class (finite, >= 0; as many as --number_classes).  Every pixel's cross-entropy is "
+                         "multiplied by the weight of its truth class; the reduction stays sum / (batch x H x W), not divided by the weights")
+    ap.add_argument("--ignore_label", dest="ignore_label", type=int, default=None,
+                    help="mask value of unlabeled pixels: they add no loss and no gradient and are left out of the accuracy and of "
+                         "--class_metrics (needs --use_augmentation 0: the augmentation's bilinear mask warp would smear the value)")
     a = ap.parse_args(argv)
+    class_weights = None
+    if a.class_weights is not None:
+        try:
+            class_weights = parse_class_weights(a.class_weights, a.number_classes)
+        except ValueError as e:
+            ap.error(str(e))
+    if a.ignore_label is not None and a.use_augmentation:
+        ap.error("--ignore_label cannot be combined with --use_augmentation 1: the augmentation warps masks by rounded bilinear interpolation, "
+                 "which smears the ignore value into neighbouring class ids; pass --use_augmentation 0")
     tr = te = None
     if a.synthetic:
         parts = [int(v) for v in a.synthetic.lower().split("x")]
@@ -292,7 +344,7 @@ def main(argv=None):
     train_model(a.output_folder, a.batch_size, a.reader_count, a.train_database_filepath, a.test_database_filepath,
                 a.use_augmentation, a.number_classes, a.balance_classes, a.learning_rate, a.test_every_n_steps,
                 a.early_stopping_count, train_reader=tr, test_reader=te, max_epochs=a.max_epochs, compute_dtype=a.compute_dtype,
-                class_metrics=a.class_metrics)
+                class_metrics=a.class_metrics, class_weights=class_weights, ignore_label=a.ignore_label)
 
 
 if __name__ == "__main__":
