@@ -31,6 +31,7 @@ extern "C" {
  * (9: + unet_convT2x2_dgrad_x6_sums (the BF16x6 transposed-conv data gradient leaves the producer layer's BatchNorm-backward sums); added under 9 without a
  *  bump, because no existing signature changed and a loader binds by name: unet_confusion_scores, unet_confusion_masks (per-class metrics);
  *  unet_softmax_ce_weighted(_workspace), unet_labels_onehot_ignore, unet_confusion_scores_valid (weighted loss, unlabeled pixels);
+ *  unet_region_loss_workspace, unet_region_loss_sums, unet_region_loss_bwd (soft Dice / Tversky region term of the loss);
  *  8: round 6 -- + unet_bn_finalize_apply_any (statistics finalize merged into the apply launch); the bf16 3x3 kernels start their accumulators at the bias;
  *  7: round 5 -- no signature changed, but the operand unet_winograd_weight_transform_x6 / _fold_x6 write is laid out for the round-5 kernel
  *  (MFMA A-operand order per 64-channel tile, chunk and point row): an operand and the conv entry point that reads it must come from one library;
@@ -350,6 +351,30 @@ size_t unet_softmax_ce_weighted_workspace(long P);
 int unet_softmax_ce_weighted(const float* logits, int ldz, const int* labels_onehot, const float* class_weight, const float* pixel_weight,
                              int ignore_empty, float* prob, float* dlogits, int lddz, long P, int K, float label_smoothing, float loss_scale,
                              float grad_scale, float ce_clip_eps, float* stats_out, void* ws, size_t ws_bytes, void* stream);
+/* Region term added to that loss: soft Tversky index per image and class (alpha = beta = 0.5: soft Dice, the "CE + Dice" compound loss).  The
+ * reference has the cross-entropy only (UNet/model.py:211-215); the term keeps that call site's reduction, sum over the local images / G, so
+ * it does not depend on how a global batch is split over replicas and gradients still combine by SUM.  prob [N][HW] rows of ldp floats = the
+ * softmax unet_softmax_ce(_weighted) wrote; y = the hard one-hot row (first maximum of the label row); ignore_empty as above: an unlabeled
+ * pixel enters no sum and its dlogits row is not touched.  Per image n and class k, over the labeled pixels of that image:
+ *       I = sum p_k y_k, S = sum p_k, Y = sum y_k,  D = (1 - alpha - beta) I + alpha S + beta Y + smooth,  T = (I + smooth) / D
+ *       region = scale * sum_n sum_k c_k / (sum_j c_j) * (1 - T_nk)       (c = class_weight, fp32 [K], NULL = all 1; finite, >= 0, not all 0:
+ *       the host wrapper checks; scale = lambda / G is the caller's)
+ * sums: one pass over prob and labels + a one-workgroup finalize launch.  Sums are kept per lane in double, combined per wave, per workgroup
+ *       and over the workspace's partials in a fixed order that depends on HW alone (no floating-point atomics): the same bits run after run
+ *       and whichever batch an image arrives in.  coef_out fp32 [N][K][2] = (-scale c~_k A_nk, -scale c~_k B_nk), A = 1/D - (I + smooth)
+ *       (1 - alpha - beta)/D^2, B = -alpha (I + smooth)/D^2, computed in double: d region / d p_k of a labeled pixel = coef[0] y_k + coef[1].
+ *       stats_out fp32 [1 + K] = region, then the mean of T_nk over the N images per class.  smooth > 0 keeps an absent class or a wholly
+ *       unlabeled image finite (T = 1: no loss, no gradient).  ws: 8-byte aligned, unet_region_loss_workspace(N, HW, K) bytes.
+ * bwd:  dlogits[p][j] += p_j (g_j - sum_k p_k g_k), g_k = coef[n][k][0] y_k + coef[n][k][1], read-modify-write behind the CE kernel's store; an
+ *       addend of zero leaves the stored bits as they are, so scale = 0 changes nothing.
+ * K <= 32 (the per-class accumulators of the generic path stay in registers); K in {2, 4} with ld == K, 16-byte aligned tensors and (K = 2)
+ * an even HW take one 16-byte access per tensor and lane.  UNET_EINVAL: K > 32, smooth <= 0, alpha < 0, beta < 0, a NULL required pointer. */
+size_t unet_region_loss_workspace(int N, long HW, int K);
+int unet_region_loss_sums(const float* prob, int ldp, const int* labels_onehot, int ignore_empty, int N, long HW, int K, float alpha, float beta,
+                          float smooth, float scale, const float* class_weight, float* coef_out, float* stats_out, void* ws, size_t ws_bytes,
+                          void* stream);
+int unet_region_loss_bwd(const float* prob, int ldp, const int* labels_onehot, int ignore_empty, const float* coef, float* dlogits, int lddz,
+                         int N, long HW, int K, void* stream);
 /* np.argmax(softmax, axis=-1), UNet/inference.py:107,166 (first maximum wins) */
 int unet_argmax(const float* p, int ldp, int* out, long P, int K, void* stream);
 

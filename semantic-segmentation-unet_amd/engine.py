@@ -113,6 +113,7 @@ class Engine:
         self.loss_buf = torch.zeros(2, dtype=torch.float32, device=self.dev)             # [loss, correct]
         self.loss_stats = torch.zeros(4, dtype=torch.float32, device=self.dev)           # weighted loss: [loss, correct, valid, weight_sum]
         self.weighted_loss = False              # the last forward with labels took unet_softmax_ce_weighted (loss_stats is current)
+        self.region_stats = None                # region term of the last forward that had one: fp32 [1 + K] = [region, mean T_0 .. T_{K-1}]
         self.dropout_seed = seed
         self.ce_clip_eps = CE_CLIP_EPS
         self._eval_folded = set()               # layers whose eval-mode (moving-statistics) BatchNorm-on-load fold is current
@@ -544,7 +545,8 @@ class Engine:
         return out
 
     def forward(self, images, training=False, dropout_masks=None, labels=None, global_batch_size=None,
-                label_smoothing=0.0, want_grad=False, confusion=None, class_weights=None, pixel_weights=None, ignore_unlabeled=False):
+                label_smoothing=0.0, want_grad=False, confusion=None, class_weights=None, pixel_weights=None, ignore_unlabeled=False,
+                region=None):
         """images: fp32 [N,C,H,W] (reference input contract, UNet/imagereader.py:298-300).  Returns softmax [N,H,W,K]
         (a device tensor owned by the engine; valid until the next call).  With labels (int32 one-hot [N,H,W,K]) the
         loss and the count of correctly classified pixels land in self.loss_buf.  confusion (metrics.ConfusionMatrix, needs labels): the
@@ -553,9 +555,14 @@ class Engine:
         class_weights (fp32 [K] device tensor), pixel_weights (fp32 [N,H,W] device tensor), ignore_unlabeled: the weighted loss
         (unet_softmax_ce_weighted: w_p = class_weights[truth] * pixel_weights[p], all-zero one-hot rows left out); [loss, correct, valid,
         weight_sum] land in self.loss_stats, the first two in loss_buf as well.  Values are the caller's to validate (model.UNet does).  With
-        all three unset the launch is unet_softmax_ce, as ever."""
+        all three unset the launch is unet_softmax_ce, as ever.
+        region (needs labels) = (weight, alpha, beta, smooth, class_weights fp32 [K] device tensor or None): the soft Tversky / Dice term per
+        image (unet_region_loss_sums behind the CE launch; with want_grad unet_region_loss_bwd adds its share to dy_logits).  [region, mean
+        T per class] land in self.region_stats and loss_buf[0] (loss_stats[0]) holds CE + region.  None: not one extra launch, no buffer."""
         if confusion is not None and labels is None:
             raise ValueError("a confusion matrix needs labels")
+        if region is not None and labels is None:
+            raise ValueError("the region term needs labels")
         L, st = self.L, self._stream()
         x = images
         assert x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == self.C, "images must be fp32 [N,C,H,W]"
@@ -676,6 +683,27 @@ class Engine:
                 self.loss_buf.copy_(self.loss_stats[:2])
                 self._weights_keepalive = (cw, pw)
             self._labels_keepalive = lab
+            if region is not None:
+                lam, alpha, beta, smooth, rcw = region
+                if rcw is not None and not (torch.is_tensor(rcw) and rcw.device == prob.device and rcw.dtype == torch.float32
+                                            and tuple(rcw.shape) == (self.K,) and rcw.is_contiguous()):
+                    raise ValueError("the region term's class weights must be a contiguous fp32 tensor %s on %s" % ([self.K], prob.device))
+                coef = self._buf("region_coef", (n, self.K, 2))
+                self.region_stats = self._buf("region_stats", (1 + self.K,))
+                nbr = L.unet_region_loss_workspace(n, h * w, self.K)
+                ws = self._workspace(nbr)
+                self._timed("region_sums", self._nb(prob, lab), L.unet_region_loss_sums,
+                            _p(prob), self.K, _p(lab), int(bool(ignore_unlabeled)), n, h * w, self.K, float(alpha), float(beta), float(smooth),
+                            float(lam) / float(G), _p(rcw), _p(coef), _p(self.region_stats), _p(ws), nbr, st)
+                if want_grad:
+                    self._timed("region_bwd", self._nb(prob, lab, dl, dl), L.unet_region_loss_bwd,
+                                _p(prob), self.K, _p(lab), int(bool(ignore_unlabeled)), _p(coef), _p(dl), self.K, n, h * w, self.K, st)
+                self.loss_buf[0:1] += self.region_stats[0:1]             # the total, on the stream: no host sync
+                if self.weighted_loss:
+                    self.loss_stats[0:1] += self.region_stats[0:1]
+                self._region_keepalive = rcw
+            else:
+                self.region_stats = None
             if confusion is not None:
                 self._timed("confusion", self._nb(yl, lab), confusion.update_from_scores, yl, lab, st,
                             *((True,) if ignore_unlabeled else ()))

@@ -79,6 +79,28 @@ def check_weights(values, what, shape=None):
     return a
 
 
+def check_region(dice_weight, tversky, dice_smooth, dice_class_weights, number_classes):
+    """The region term's settings, validated on the host (the kernel checks signs only):
+    -> None when dice_weight == 0, else (weight, alpha, beta, smooth, class weights as an fp32 numpy array or None)"""
+    try:
+        alpha, beta = (float(v) for v in tversky)
+    except (TypeError, ValueError):
+        raise ValueError("tversky must be a pair (alpha, beta)")
+    lam, smooth = float(dice_weight), float(dice_smooth)
+    if not all(np.isfinite(v) for v in (lam, alpha, beta, smooth)):
+        raise ValueError("dice_weight, tversky and dice_smooth must be finite")
+    if lam < 0 or alpha < 0 or beta < 0:
+        raise ValueError("dice_weight, tversky alpha and beta must be >= 0")
+    if smooth <= 0:
+        raise ValueError("dice_smooth must be > 0")
+    cw = None
+    if dice_class_weights is not None:
+        cw = check_weights(dice_class_weights, "dice_class_weights", (number_classes,))
+        if not (cw > 0).any():
+            raise ValueError("dice_class_weights must not all be zero")
+    return None if lam == 0 else (lam, alpha, beta, smooth, cw)
+
+
 class _KerasLikeModel:
     """`unet.get_keras_model()`: callable as m(x, training=False) with x fp32 [N,C,H,W] (numpy or torch), returning the
     softmax [N,H,W,K] (reference UNet/inference.py:105,164; UNet/model.py:177,209,239)."""
@@ -119,8 +141,14 @@ class UNet:
     RADIUS = 96
 
     def __init__(self, number_classes, global_batch_size, number_channels, learning_rate=3e-4, label_smoothing=0,
-                 device="cuda", seed=0, compute_dtype=None, class_weights=None, ignore_unlabeled=False):
-        """class_weights (length number_classes, finite, >= 0), ignore_unlabeled, and the steps' pixel_weights: the weighted loss
+                 device="cuda", seed=0, compute_dtype=None, class_weights=None, ignore_unlabeled=False,
+                 dice_weight=0.0, tversky=(0.5, 0.5), dice_smooth=1.0, dice_class_weights=None):
+        """dice_weight (lambda >= 0), tversky = (alpha, beta) >= 0, dice_smooth (s > 0), dice_class_weights (length number_classes, >= 0, not
+        all zero; normalised to sum 1): the compound loss CE + lambda / G * sum over the local images n and the classes k of c~_k (1 - T_nk),
+        T_nk = (I + s) / ((1 - alpha - beta) I + alpha S + beta Y + s) the soft Tversky index of image n (alpha = beta = 0.5: soft Dice) over
+        its labeled pixels; class_weights and pixel_weights do not enter it.  Per image and divided by the global batch size, like the
+        cross-entropy: independent of how a batch is split over replicas.  dice_weight = 0: the launches of before.
+        class_weights (length number_classes, finite, >= 0), ignore_unlabeled, and the steps' pixel_weights: the weighted loss
         loss = sum_p class_weights[truth_p] * pixel_weights[p] * ce_p / (G H W) -- Keras' sample_weight under the reference's reduction, NOT
         divided by the weight sum; with ignore_unlabeled a pixel whose one-hot row is all zero (feed.DeviceFeed(ignore_label=...)) adds no
         loss and no gradient and leaves the accuracy's numerator and denominator.  All unset: the reference's loss, the launches of before."""
@@ -129,12 +157,16 @@ class UNet:
         self.number_classes = number_classes
         self.global_batch_size = global_batch_size
         self.label_smoothing = label_smoothing
+        region = check_region(dice_weight, tversky, dice_smooth, dice_class_weights, number_classes)     # before anything touches the device
         self.engine = Engine(number_classes, number_channels, device=device, seed=seed)
         self.ignore_unlabeled = bool(ignore_unlabeled)
         self.class_weights = None
         if class_weights is not None:                            # validated and uploaded once
             cw = check_weights(class_weights, "class_weights", (number_classes,))
             self.class_weights = torch.as_tensor(cw).to(self.engine.dev)
+        self.region = None                                       # Engine.forward(region=...): class weights uploaded once
+        if region is not None:
+            self.region = region[:4] + (torch.as_tensor(region[4]).to(self.engine.dev) if region[4] is not None else None,)
         if compute_dtype is not None:        # "fp32" (reference arithmetic) | "bf16" (mixed precision the reference leaves commented
             if compute_dtype not in ("fp32", "bf16"):                                  # out, UNet/train.py:52-54)
                 raise ValueError("compute_dtype must be 'fp32' or 'bf16'")
@@ -232,6 +264,8 @@ class UNet:
             kw["pixel_weights"] = self._pixel_weights(pixel_weights, images)
         if self.ignore_unlabeled:
             kw["ignore_unlabeled"] = True
+        if self.region is not None:
+            kw["region"] = self.region
         return kw
 
     def train_step(self, inputs, dropout_masks=None, confusion=None, pixel_weights=None):

@@ -65,10 +65,27 @@ def parse_class_weights(text, number_classes):
     return [float(v) for v in unet_model_module.check_weights(w, "--class_weights")]
 
 
+def region_settings(dice_weight=0.0, tversky_alpha=0.5, tversky_beta=0.5, dice_smooth=1.0, dice_class_weights=None, number_classes=2):
+    """`--dice_weight`, `--tversky_alpha`, `--tversky_beta`, `--dice_smooth`, `--dice_class_weights w0,w1,...` -> the keywords of model.UNet
+    for the region term ({} when the weight is 0: the network is then built as before); ValueError names the option at fault."""
+    cw = dice_class_weights
+    if isinstance(cw, str):
+        try:
+            cw = parse_class_weights(cw, number_classes)
+        except ValueError as e:
+            raise ValueError(str(e).replace("--class_weights", "--dice_class_weights"))
+    if unet_model_module.check_region(dice_weight, (tversky_alpha, tversky_beta), dice_smooth, cw, number_classes) is None:
+        return {}
+    kw = {"dice_weight": float(dice_weight), "tversky": (float(tversky_alpha), float(tversky_beta)), "dice_smooth": float(dice_smooth)}
+    if cw is not None:
+        kw["dice_class_weights"] = [float(v) for v in cw]
+    return kw
+
+
 def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, test_lmdb_filepath, use_augmentation,
                 number_classes, balance_classes, learning_rate, test_every_n_steps, early_stopping_count,
                 train_reader=None, test_reader=None, max_epochs=None, quiet=False, compute_dtype=None, unet_factory=None,
-                class_metrics=False, class_weights=None, ignore_label=None):
+                class_metrics=False, class_weights=None, ignore_label=None, region=None):
     """unet_factory (tests): callable(number_classes, global_batch_size, number_channels, learning_rate, device=..., compute_dtype=...)
     standing in for model.UNet, so the loop semantics can be checked without a GPU; the default is the HIP-backed class, which
     refuses to run anywhere but on an MI355X.
@@ -80,11 +97,20 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
 
     class_weights (opt-in extra, one per class) weight every pixel's loss by its truth class; ignore_label (opt-in extra) is the mask value
     of unlabeled pixels: the feeds turn it into an all-zero one-hot row, and the network (`ignore_unlabeled=True`), the accuracy and the
-    test-epoch confusion matrix leave such pixels out.  Both reach the network as keywords only when set."""
+    test-epoch confusion matrix leave such pixels out.  Both reach the network as keywords only when set.
+
+    region (opt-in extra; region_settings()'s dict): the soft Dice / Tversky term of the loss (model.UNet(dice_weight=, tversky=, dice_smooth=,
+    dice_class_weights=)).  Train and test steps then return CE + region, so test_loss.csv, the best checkpoint and early stopping follow
+    the compound loss; with class_metrics the test epoch's line also carries the mean soft index per class."""
     say = (lambda *a: None) if quiet else print
     # the weighted-loss options are checked before anything is opened
     if class_weights is not None:
         class_weights = [float(v) for v in unet_model_module.check_weights(class_weights, "class_weights", (number_classes,))]
+    if region:
+        region = dict(region)
+        if unet_model_module.check_region(region.get("dice_weight", 0.0), region.get("tversky", (0.5, 0.5)), region.get("dice_smooth", 1.0),
+                                          region.get("dice_class_weights"), number_classes) is None:
+            region = None
     if ignore_label is not None:
         ignore_label = int(ignore_label)
         if not 0 <= ignore_label <= 255:
@@ -177,6 +203,8 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
             loss_kw["class_weights"] = class_weights
         if ignore_label is not None:
             loss_kw["ignore_unlabeled"] = True
+        if region:
+            loss_kw.update(region)
         net = (unet_factory or unet_model_module.UNet)(number_classes, global_batch_size, number_channels, learning_rate,
                                                        device=dev_, compute_dtype=compute_dtype, **loss_kw)
         strategy = None
@@ -240,12 +268,17 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
                 if step % LABEL_CHECK_EVERY == 0:
                     check_labels()
             epoch_test_loss = []
+            soft_sum, soft_steps = None, 0                         # region term: the steps' mean soft index per class, summed on the device
             step = 0
             while step <= test_epoch_size:
                 images, labels = next(test_batches)
                 loss_value = net.dist_test_step(strategy, (images.to(dev_, non_blocking=True), labels.to(dev_, non_blocking=True),
                                                            test_loss_metric, test_acc_metric), **step_kw)
                 epoch_test_loss.append(loss_value.numpy())
+                rs = getattr(getattr(net, "engine", None), "region_stats", None) if (region and test_confusion is not None) else None
+                if rs is not None:
+                    soft_sum = rs[1:].clone() if soft_sum is None else soft_sum + rs[1:]
+                    soft_steps += 1
                 step += 1
             test_loss.append(np.mean(epoch_test_loss))             # (kept as numpy's fp32 scalar: test_loss.csv then carries the reference's text, UNet/train.py:162,173-176)
             check_labels()                                         # before the csv / checkpoint of this epoch are written
@@ -259,6 +292,12 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
                 test_confusion.reset_states()
                 if rank == 0:
                     say("Test Epoch: {}: mean IoU = {} IoU per class = {}".format(epoch, cls["mean_iou"], [float(v) for v in cls["iou"]]))
+                if soft_sum is not None:                           # (every rank: the sum over the replicas is a collective)
+                    if strategy is not None:
+                        soft_sum = strategy.reduce_sum(soft_sum)
+                    soft = [float(v) / (soft_steps * world) for v in soft_sum.tolist()]
+                    if rank == 0:
+                        say("Test Epoch: {}: mean soft Tversky index per class = {}".format(epoch, soft))
                 if writers:
                     writers[1].scalar("mean_iou", cls["mean_iou"], (epoch + 1) * train_epoch_size)
                     for k, v in enumerate(cls["iou"]):
@@ -322,7 +361,19 @@ def main(argv=None):
     ap.add_argument("--ignore_label", dest="ignore_label", type=int, default=None,
                     help="mask value of unlabeled pixels: they add no loss and no gradient and are left out of the accuracy and of "
                          "--class_metrics (needs --use_augmentation 0: the augmentation's bilinear mask warp would smear the value)")
+    ap.add_argument("--dice_weight", dest="dice_weight", type=float, default=0.0,
+                    help="lambda >= 0: adds lambda x the soft Dice / Tversky term (per image, 1 - index averaged over the classes, summed over the "
+                         "batch / global batch size) to the cross-entropy; 0 = cross-entropy only")
+    ap.add_argument("--tversky_alpha", dest="tversky_alpha", type=float, default=0.5, help="weight of false positives in the index (0.5, 0.5: Dice)")
+    ap.add_argument("--tversky_beta", dest="tversky_beta", type=float, default=0.5, help="weight of false negatives in the index")
+    ap.add_argument("--dice_smooth", dest="dice_smooth", type=float, default=1.0, help="smoothing constant s > 0 of the index")
+    ap.add_argument("--dice_class_weights", dest="dice_class_weights", type=str, default=None,
+                    help="w0,w1,...: weight of each class's index in the term (finite, >= 0, not all zero; normalised to sum 1)")
     a = ap.parse_args(argv)
+    try:
+        region = region_settings(a.dice_weight, a.tversky_alpha, a.tversky_beta, a.dice_smooth, a.dice_class_weights, a.number_classes)
+    except ValueError as e:
+        ap.error(str(e))
     class_weights = None
     if a.class_weights is not None:
         try:
@@ -344,7 +395,7 @@ def main(argv=None):
     train_model(a.output_folder, a.batch_size, a.reader_count, a.train_database_filepath, a.test_database_filepath,
                 a.use_augmentation, a.number_classes, a.balance_classes, a.learning_rate, a.test_every_n_steps,
                 a.early_stopping_count, train_reader=tr, test_reader=te, max_epochs=a.max_epochs, compute_dtype=a.compute_dtype,
-                class_metrics=a.class_metrics, class_weights=class_weights, ignore_label=a.ignore_label)
+                class_metrics=a.class_metrics, class_weights=class_weights, ignore_label=a.ignore_label, region=region or None)
 
 
 if __name__ == "__main__":
