@@ -32,6 +32,7 @@ extern "C" {
  *  bump, because no existing signature changed and a loader binds by name: unet_confusion_scores, unet_confusion_masks (per-class metrics);
  *  unet_softmax_ce_weighted(_workspace), unet_labels_onehot_ignore, unet_confusion_scores_valid (weighted loss, unlabeled pixels);
  *  unet_region_loss_workspace, unet_region_loss_sums, unet_region_loss_bwd (soft Dice / Tversky region term of the loss);
+ *  unet_image_tile_gather_tta, unet_prob_accumulate, unet_argmax_paste_conf (test-time augmentation and confidence maps of the inference pipeline);
  *  8: round 6 -- + unet_bn_finalize_apply_any (statistics finalize merged into the apply launch); the bf16 3x3 kernels start their accumulators at the bias;
  *  7: round 5 -- no signature changed, but the operand unet_winograd_weight_transform_x6 / _fold_x6 write is laid out for the round-5 kernel
  *  (MFMA A-operand order per 64-channel tile, chunk and point row): an operand and the conv entry point that reads it must come from one library;
@@ -394,6 +395,31 @@ int unet_image_tile_gather(const void* img, int dtype, int H, int W, int C, cons
                            int y0, int x0, int th, int tw, float* out, void* stream);
 int unet_argmax_paste(const float* prob, int ldp, int th, int tw, int K, int oy, int ox, int zh, int zw,
                       void* mask, int elem_size, long pitch, int my, int mx, int Hm, int Wm, void* stream);
+
+/* ---- test-time augmentation and confidence maps for the pipeline above (csrc/inference_tta.hip; the reference forwards a tile once and keeps
+ * the arg-max only) -- per tile and per transform: gather_tta -> forward -> prob_accumulate, then one argmax_paste(_conf) ----------------------
+ * Transform code t in 0..7, the dihedral group of the square; bit 2 = transpose the two spatial axes, bit 1 = flip rows, bit 0 = flip columns,
+ * applied in that order to the plain tile G [C][th][tw]:
+ *       X = G;  if (t & 4) X = X.transpose(0, 2, 1);  if (t & 2) X = X[:, ::-1, :];  if (t & 1) X = X[:, :, ::-1]
+ * X is [C][th'][tw'] with (th', tw') = (tw, th) when t & 4, else (th, tw); t = 0 is the identity.  The inverse on an NHWC softmax
+ * P[th'][tw'][K] undoes the steps in reverse: flip columns, flip rows, transpose back to [th][tw][K].
+ * tile_gather_tta: the transform t of what unet_image_tile_gather writes for the same arguments, straight into the network's input
+ *       [1][C][th'][tw'] -- a pure permutation of the same values.  Argument rules of unet_image_tile_gather plus 0 <= transform <= 7
+ *       (transform 0 IS unet_image_tile_gather).  The transposing codes stage 32 x 32 pixels through LDS (pitch 33): coalesced on both sides.
+ * prob_accumulate: prob = softmax of the transformed tile, [th'][tw'] pixels of ldp floats; acc = [th][tw] pixels of lda floats in PLAIN tile
+ *       coordinates.  first != 0: acc[y][x][k] = the inverse-transformed prob; else acc[y][x][k] = acc[y][x][k] + that value, one fp32
+ *       addition.  No atomics, one owner per element: after calls p_0 (first), p_1, ... acc holds ((p_0 + p_1) + p_2) + ... exactly.
+ *       Floats k >= K of a pixel are neither read nor written.  UNET_EINVAL: acc overlaps prob, K < 1, lda < K, ldp < K, transform not in 0..7.
+ * argmax_paste_conf: unet_argmax_paste (same zone, same clipping against (Hm, Wm), same first maximum, compared on the UNSCALED acc, nothing
+ *       outside the zone touched) that also writes conf[my + r][mx + c] = max_k acc * scale (rows of conf_pitch >= Wm floats; may be NULL) and
+ *       prob_out[my + r][mx + c][k] = acc[k] * scale (dense [Hm][Wm][K]; may be NULL).  Both NULL: UNET_EINVAL (that is unet_argmax_paste).
+ *       The caller passes scale = 1 / n for n accumulated transforms, n a power of two, so the scaling is exact. */
+int unet_image_tile_gather_tta(const void* img, int dtype, int H, int W, int C, const float* mean, const float* stddev,
+                               int y0, int x0, int th, int tw, int transform, float* out, void* stream);
+int unet_prob_accumulate(const float* prob, int ldp, int th, int tw, int K, int transform, int first, float* acc, int lda, void* stream);
+int unet_argmax_paste_conf(const float* acc, int lda, int th, int tw, int K, float scale, int oy, int ox, int zh, int zw,
+                           void* mask, int elem_size, long pitch, int my, int mx, int Hm, int Wm,
+                           float* conf, long conf_pitch, float* prob_out, void* stream);
 
 /* ---- per-class segmentation metrics: the K x K confusion matrix behind IoU / Dice / precision / recall (csrc/metrics.hip; the reference reports
  * pixel accuracy only, UNet/train.py:106,108) ----------------------------------------------------------------------------------------------

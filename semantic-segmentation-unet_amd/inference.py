@@ -16,6 +16,7 @@ written by a worker thread while image i + 1 is segmented.  `_inference` / `_inf
 `--host_pipeline`) are the reference's line-for-line host loop.
 """
 import argparse
+import collections
 import ctypes
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -153,24 +154,104 @@ def _host_confusion(mask, truth, confusion, ignore_label=-1):
     confusion.out_of_range += int((keep & ~inside).sum())
 
 
-def _segment_host_pipeline(raw, unet, tile_size=TILE_SIZE, truth=None, confusion=None, ignore_label=-1):
+TTA_CHOICES = (1, 2, 4, 8)
+SegmentResult = collections.namedtuple("SegmentResult", ["mask", "confidence", "probabilities"])
+
+
+def _check_tta(tta):
+    if isinstance(tta, bool) or tta not in TTA_CHOICES:
+        raise ValueError("tta must be one of %s (the identity, + the horizontal flip, all flips, the whole dihedral group), not %r"
+                         % (list(TTA_CHOICES), tta))
+    return int(tta)
+
+
+def tta_apply(x_chw, t):
+    """Transform code `t` (0..7) on a [C, th, tw] tile: bit 2 = transpose the two spatial axes, then bit 1 = flip rows, then bit 0 = flip
+    columns -- the dihedral group of the square, 0 the identity (what `unet_image_tile_gather_tta` writes).  A view, not a copy."""
+    if not 0 <= t <= 7:
+        raise ValueError("transform code %r is not in 0..7" % (t,))
+    x = np.asarray(x_chw)
+    if t & 4:
+        x = x.transpose(0, 2, 1)
+    if t & 2:
+        x = x[:, ::-1, :]
+    if t & 1:
+        x = x[:, :, ::-1]
+    return x
+
+
+def tta_invert(p_hwk, t):
+    """The inverse of `tta_apply(., t)` on the NHWC side, a [th', tw', K] softmax: the steps undone in reverse order -- flip columns, flip
+    rows, transpose back -- so that pixel (y, x) is the tile's again (what `unet_prob_accumulate` reads).  A view, not a copy."""
+    if not 0 <= t <= 7:
+        raise ValueError("transform code %r is not in 0..7" % (t,))
+    p = np.asarray(p_hwk)
+    if t & 1:
+        p = p[:, ::-1, :]
+    if t & 2:
+        p = p[::-1, :, :]
+    if t & 4:
+        p = p.transpose(1, 0, 2)
+    return p
+
+
+def _segment_tta_host(img, unet, tile_size, tta=1):
+    """Z-scored HWC image -> (mask int32 [H, W], confidence fp32 [H, W], probabilities fp32 [H, W, K]): the host statement of the device
+    pipeline with test-time augmentation.  Walks `tile_plan`; per tile the `tta` transforms 0 .. tta - 1 go through the eval forward with
+    numpy flips around it and are summed in that order in float32, acc = ((P_0 + P_1) + P_2) + ...; mask = first maximum of the
+    UNSCALED sum, confidence and probabilities = the sum times float32(1 / tta) (a power of two: exact).  Bit for bit what
+    `segment_image` returns, given that the eval forward is deterministic for one input."""
+    tta = _check_tta(tta)
+    img, pad_y, pad_x = _pad_to_factor(img)
+    hp, wp = img.shape[:2]
+    tiled = hp > tile_size or wp > tile_size
+    plan = tile_plan(hp, wp, tile_size, unet.estimate_radius() if tiled else None)
+    e, k = unet.engine, unet.number_classes
+    total = np.empty((hp, wp, k), np.float32)
+    for (ty, tx, th, tw), (zy, zx, zh, zw) in plan:
+        g = img[ty:ty + th, tx:tx + tw].transpose(2, 0, 1)
+        acc = None
+        for t in range(tta):
+            x = torch.as_tensor(np.ascontiguousarray(tta_apply(g, t))[None].astype(np.float32))
+            p = tta_invert(e.forward(x, training=False)[0].cpu().numpy(), t)
+            if acc is None:
+                acc = p.copy()
+            else:
+                acc += p
+        oy, ox = zy - ty, zx - tx
+        total[zy:zy + zh, zx:zx + zw] = acc[oy:oy + zh, ox:ox + zw]
+    total = total[:hp - pad_y, :wp - pad_x]
+    scale = np.float32(1.0 / tta)
+    return np.argmax(total, axis=-1).astype(np.int32), total.max(axis=-1) * scale, total * scale
+
+
+def _segment_host_pipeline(raw, unet, tile_size=TILE_SIZE, truth=None, confusion=None, ignore_label=-1, tta=1, return_confidence=False,
+                           return_probabilities=False):
     """the reference's loop (UNet/inference.py:201-213): float32, z-score over the whole image, whole-image or tiled driver.  With
-    truth / confusion the mask is scored on the host (the counts `segment_image` takes on the device)."""
+    truth / confusion the mask is scored on the host (the counts `segment_image` takes on the device).  tta / return_confidence /
+    return_probabilities: as `segment_image`, through `_segment_tta_host`."""
+    tta = _check_tta(tta)
     if truth is not None or confusion is not None:
         truth = _check_truth(truth, confusion, raw.shape[0], raw.shape[1])
     img = raw.astype(np.float32)
     hwc = img[:, :, None] if img.ndim == 2 else img
     img = zscore_normalize(hwc.transpose(2, 0, 1)).transpose(1, 2, 0)
-    if img.shape[0] > tile_size or img.shape[1] > tile_size:
+    conf = probs = None
+    if tta > 1 or return_confidence or return_probabilities:
+        mask, conf, probs = _segment_tta_host(img, unet, tile_size, tta)
+    elif img.shape[0] > tile_size or img.shape[1] > tile_size:
         mask = _inference_tiling(img, unet, tile_size)
     else:
         mask = _inference(img, unet)
     if confusion is not None:
         _host_confusion(mask, truth, confusion, ignore_label)
+    if return_confidence or return_probabilities:
+        return SegmentResult(mask, conf if return_confidence else None, probs if return_probabilities else None)
     return mask
 
 
-def segment_image(img, unet, tile_size=TILE_SIZE, radius=None, truth=None, confusion=None, ignore_label=-1):
+def segment_image(img, unet, tile_size=TILE_SIZE, radius=None, truth=None, confusion=None, ignore_label=-1, tta=1, return_confidence=False,
+                  return_probabilities=False):
     """Raw image (HW or HWC, any dtype `_read` returns) -> class map [H, W], the mask `_inference` / `_inference_tiling` compute on the
     z-scored image, bit for bit, with the whole pipeline on the device: one upload of the image in its raw dtype (uint8 / uint16 / fp32;
     anything else is converted to fp32 on the host first, as the host path does), then per entry of `tile_plan` gather (reflect padding,
@@ -187,7 +268,17 @@ def segment_image(img, unet, tile_size=TILE_SIZE, radius=None, truth=None, confu
     are, beside the image, from pinned memory; the rest as int32) and a metrics.ConfusionMatrix.  After the last paste ONE
     `unet_confusion_masks` launch on the same stream scores the device mask -- before the download's synchronise, still the only one --
     and adds the K x K counts to `confusion` (truth == ignore_label skipped, -1 skips nothing; labels outside [0, K) counted in
-    confusion.out_of_range).  The returned mask is unchanged by it."""
+    confusion.out_of_range).  The returned mask is unchanged by it.
+
+    tta in {1, 2, 4, 8} (anything else: ValueError, before any device work): test-time augmentation with the transforms 0 .. tta - 1 of
+    `tta_apply` -- 2 adds the horizontal flip, 4 is all flips, 8 the whole dihedral group of the square.  Per tile and per transform:
+    `unet_image_tile_gather_tta` -> eval forward -> `unet_prob_accumulate` (enqueued before the next forward, which reuses the softmax
+    buffer), then the paste of the arg-max of the sum.  return_confidence / return_probabilities: the return value becomes
+    `SegmentResult(mask, confidence, probabilities)` -- fp32 [H, W] probability of the winning class, fp32 [H, W, K] mean softmax, None for
+    what was not asked -- written by `unet_argmax_paste_conf` (with tta = 1 straight from the softmax, no accumulate), each downloaded once
+    behind the same single synchronise.  `_segment_tta_host` states the arithmetic; both agree bit for bit.  With tta = 1 and nothing
+    asked for, the launches and the returned array are exactly those described above."""
+    tta = _check_tta(tta)
     img = np.asarray(img)
     if img.ndim not in (2, 3):
         raise IOError("Invalid number of dimensions for input image. Expecting HW or HWC dimension ordering.")
@@ -202,7 +293,8 @@ def segment_image(img, unet, tile_size=TILE_SIZE, radius=None, truth=None, confu
         truth = _check_truth(truth, confusion, h, w)
     hp, wp = h + (-h) % SIZE_FACTOR, w + (-w) % SIZE_FACTOR
     if h == 1 or w == 1:                             # padded to 16: unet_image_tile_gather refuses it (UNET_EINVAL)
-        return _segment_host_pipeline(img, unet, tile_size, truth=truth, confusion=confusion, ignore_label=ignore_label)
+        return _segment_host_pipeline(img, unet, tile_size, truth=truth, confusion=confusion, ignore_label=ignore_label, tta=tta,
+                                      return_confidence=return_confidence, return_probabilities=return_probabilities)
     e, L = unet.engine, lib()
     dev = e.dev
     if scoring and (confusion.device != torch.empty(0, device=dev).device or confusion.number_classes != unet.number_classes):
@@ -225,22 +317,56 @@ def segment_image(img, unet, tile_size=TILE_SIZE, radius=None, truth=None, confu
     mask = torch.empty((h, w), dtype=mdt, device=dev)
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())
     tiles = {}
+    extra = return_confidence or return_probabilities
+    conf = torch.empty((h, w), dtype=torch.float32, device=dev) if return_confidence else None
+    probs = torch.empty((h, w, k), dtype=torch.float32, device=dev) if return_probabilities else None
+    accs = {}                                        # (th, tw) -> [th, tw, K] sum of the inverse-transformed softmaxes, tile coordinates
     for (ty, tx, th, tw), (zy, zx, zh, zw) in plan:
-        x = tiles.get((th, tw))
-        if x is None:
-            x = tiles[(th, tw)] = torch.empty((1, c, th, tw), dtype=torch.float32, device=dev)
+        if tta == 1 and not extra:
+            x = tiles.get((th, tw))
+            if x is None:
+                x = tiles[(th, tw)] = torch.empty((1, c, th, tw), dtype=torch.float32, device=dev)
+            st = e._stream()
+            L.unet_image_tile_gather(ptr(raw), _RAW_DTYPES[img.dtype], h, w, c, ptr(coef[0]), ptr(coef[1]), ty, tx, th, tw, ptr(x), st)
+            prob = e.forward(x, training=False)
+            L.unet_argmax_paste(ptr(prob), k, th, tw, k, zy - ty, zx - tx, zh, zw, ptr(mask), mask.element_size(), w, zy, zx, h, w, st)
+            continue
         st = e._stream()
-        L.unet_image_tile_gather(ptr(raw), _RAW_DTYPES[img.dtype], h, w, c, ptr(coef[0]), ptr(coef[1]), ty, tx, th, tw, ptr(x), st)
-        prob = e.forward(x, training=False)
-        L.unet_argmax_paste(ptr(prob), k, th, tw, k, zy - ty, zx - tx, zh, zw, ptr(mask), mask.element_size(), w, zy, zx, h, w, st)
+        for t in range(tta):
+            shape = (tw, th) if t & 4 else (th, tw)  # a transposed tile is a shape of its own
+            x = tiles.get(shape)
+            if x is None:
+                x = tiles[shape] = torch.empty((1, c) + shape, dtype=torch.float32, device=dev)
+            L.unet_image_tile_gather_tta(ptr(raw), _RAW_DTYPES[img.dtype], h, w, c, ptr(coef[0]), ptr(coef[1]), ty, tx, th, tw, t, ptr(x), st)
+            src = e.forward(x, training=False)       # (the engine's softmax buffer: valid until the next forward only)
+            if tta > 1:
+                acc = accs.get((th, tw))
+                if acc is None:
+                    acc = accs[(th, tw)] = torch.empty((th, tw, k), dtype=torch.float32, device=dev)
+                L.unet_prob_accumulate(ptr(src), k, th, tw, k, t, 1 if t == 0 else 0, ptr(acc), k, st)
+        if tta > 1:
+            src = acc
+        if extra:
+            L.unet_argmax_paste_conf(ptr(src), k, th, tw, k, 1.0 / tta, zy - ty, zx - tx, zh, zw, ptr(mask), mask.element_size(), w, zy, zx, h, w,
+                                     None if conf is None else ptr(conf), w, None if probs is None else ptr(probs), st)
+        else:
+            L.unet_argmax_paste(ptr(src), k, th, tw, k, zy - ty, zx - tx, zh, zw, ptr(mask), mask.element_size(), w, zy, zx, h, w, st)
     if scoring:
         confusion.update_from_masks(mask, truth_dev, ignore_label, st)
     out = torch.empty((h, w), dtype=mdt, pin_memory=True)
     out.copy_(mask, non_blocking=True)
+    if conf is not None:
+        conf_out = torch.empty((h, w), dtype=torch.float32, pin_memory=True)
+        conf_out.copy_(conf, non_blocking=True)
+    if probs is not None:
+        probs_out = torch.empty((h, w, k), dtype=torch.float32, pin_memory=True)
+        probs_out.copy_(probs, non_blocking=True)
     torch.cuda.current_stream().synchronize()
     del raw_host, coef_host                          # (pinned sources of the uploads: alive until the synchronise above)
     if scoring:
         del truth_host
+    if extra:
+        return SegmentResult(out.numpy(), conf_out.numpy() if conf is not None else None, probs_out.numpy() if probs is not None else None)
     return out.numpy()
 
 
@@ -254,10 +380,11 @@ def _read(path):
 def _write_bigtiff_tiled(path, mask, tile=1024, level=6):
     """The file `skimage.io.imsave(path, mask, compress=6, bigtiff=True, tile=(1024, 1024))` asks tifffile for (reference
     UNet/inference.py:221-222): a little-endian BigTIFF, one image, 1024 x 1024 tiles (edge tiles zero-padded to full size), every tile
-    zlib-deflated at level 6 (Compression = 8, Adobe deflate), one sample per pixel, MinIsBlack."""
+    zlib-deflated at level 6 (Compression = 8, Adobe deflate), one sample per pixel, MinIsBlack.  A float32 array (the confidence map of
+    --confidence_folder) is written the same way with SampleFormat 3 (IEEE floating point)."""
     import struct
     import zlib
-    assert mask.ndim == 2 and mask.dtype in (np.uint8, np.uint16, np.int32)
+    assert mask.ndim == 2 and mask.dtype in (np.uint8, np.uint16, np.int32, np.float32)
     h, w = mask.shape
     ty, tx = (h + tile - 1) // tile, (w + tile - 1) // tile
     tiles = []
@@ -269,7 +396,7 @@ def _write_bigtiff_tiled(path, mask, tile=1024, level=6):
             tiles.append(zlib.compress(t.astype(mask.dtype.newbyteorder("<")).tobytes(), level))
     n = len(tiles)
     # (tag, type, count, value): types 3 = SHORT, 4 = LONG, 16 = LONG8; tags in ascending order
-    fmt = 2 if mask.dtype == np.int32 else 1
+    fmt = 3 if mask.dtype == np.float32 else 2 if mask.dtype == np.int32 else 1      # SampleFormat: IEEE float, signed, unsigned
     entries = [(256, 4, 1, w), (257, 4, 1, h), (258, 3, 1, mask.dtype.itemsize * 8), (259, 3, 1, 8), (262, 3, 1, 1), (277, 3, 1, 1),
                (284, 3, 1, 1), (322, 4, 1, tile), (323, 4, 1, tile), (324, 16, n, None), (325, 16, n, None), (339, 3, 1, fmt)]
     ifd_off = 16
@@ -328,7 +455,7 @@ def mask_dtype(max_label):
 
 
 def inference(checkpoint_filepath, image_folder, output_folder, number_classes, number_channels, image_format, compute_dtype=None,
-              host_pipeline=False, mask_folder=None, ignore_label=-1):
+              host_pipeline=False, mask_folder=None, ignore_label=-1, tta=1, confidence_folder=None):
     """host_pipeline: the reference's host loop per tile (`_inference` / `_inference_tiling`) instead of `segment_image`; the masks are
     the same.  The file of image i is written by one worker thread while image i + 1 is segmented: files appear in order, every write
     has finished when this returns, and the first exception of a write is raised here.
@@ -336,7 +463,16 @@ def inference(checkpoint_filepath, image_folder, output_folder, number_classes, 
     mask_folder (opt-in extra): ground-truth class maps with the images' file names.  Every mask is scored against its ground truth
     (on the device, or on the host with host_pipeline: the same counts) and the output folder also receives `scores.csv` -- one row per
     image and a final `total` row: image, pixel_accuracy, mean_iou, iou_0.., dice_0.. -- and `confusion.npy`, the summed int64 matrix
-    (rows = truth).  A missing ground-truth file is an error before anything is segmented."""
+    (rows = truth).  A missing ground-truth file is an error before anything is segmented.
+
+    tta (opt-in extra): test-time augmentation, see `segment_image`; the masks written (and scored) are those of the averaged softmax.
+    confidence_folder (opt-in extra): receives one fp32 [H, W] file per image with the image's name, the probability of the winning
+    class, written by the same worker thread right after the mask (.npy, or a TIFF like the mask's when the format is a TIFF)."""
+    tta = _check_tta(tta)
+    if confidence_folder is not None:
+        if image_format != "npy" and "tif" not in image_format:
+            raise ValueError("--confidence_folder writes float32 files: --image_format must be npy or a TIFF, not %s" % image_format)
+        os.makedirs(confidence_folder, exist_ok=True)
     os.makedirs(output_folder, exist_ok=True)
     names = sorted(f for f in os.listdir(image_folder) if f.endswith("." + image_format))
     if mask_folder is not None:
@@ -359,7 +495,12 @@ def inference(checkpoint_filepath, image_folder, output_folder, number_classes, 
             if mask_folder is not None:
                 per_image.reset_states()
                 kw = dict(truth=_read(os.path.join(mask_folder, name)), confusion=per_image, ignore_label=ignore_label)
+            if tta != 1 or confidence_folder is not None:
+                kw.update(tta=tta, return_confidence=confidence_folder is not None)
             seg = _segment_host_pipeline(raw, unet, **kw) if host_pipeline else segment_image(raw, unet, **kw)
+            conf = None
+            if confidence_folder is not None:
+                seg, conf = seg.mask, seg.confidence
             if mask_folder is not None:
                 counts = per_image.result()
                 total += counts
@@ -368,6 +509,8 @@ def inference(checkpoint_filepath, image_folder, output_folder, number_classes, 
             if writes and writes[-1].done() and writes[-1].exception() is not None:
                 break                                 # a write has failed: segment no further images, report it below
             writes.append(writer.submit(_write, os.path.join(output_folder, name), seg, image_format))
+            if conf is not None:                      # the same single worker: behind the mask of this image, before the next one's
+                writes.append(writer.submit(_write, os.path.join(confidence_folder, name), conf, image_format))
     finally:
         writer.shutdown(wait=True)                    # drain: every submitted write has run (or failed) before this returns
     for f in writes:
@@ -396,9 +539,16 @@ def main(argv=None):
                          "pixel accuracy, mean IoU, per-class IoU and Dice) and confusion.npy into the output folder")
     ap.add_argument("--ignore_label", dest="ignore_label", type=int, default=-1,
                     help="with --mask_folder: ground-truth label whose pixels are not scored (-1: score every pixel)")
+    ap.add_argument("--tta", dest="tta", type=int, choices=list(TTA_CHOICES), default=1,
+                    help="opt-in extra: test-time augmentation -- average the softmax over the first N transforms of the square's dihedral "
+                         "group (2: + horizontal flip, 4: all flips, 8: + the transpositions); N forwards per tile")
+    ap.add_argument("--confidence_folder", dest="confidence_folder", type=str, default=None,
+                    help="opt-in extra: also write the probability of the winning class per pixel, one float32 file per image with the "
+                         "image's name (.npy or TIFF by --image_format)")
     a = ap.parse_args(argv)
     inference(a.checkpoint_filepath, a.image_folder, a.output_folder, a.number_classes, a.number_channels, a.image_format,
-              compute_dtype=a.compute_dtype, host_pipeline=a.host_pipeline, mask_folder=a.mask_folder, ignore_label=a.ignore_label)
+              compute_dtype=a.compute_dtype, host_pipeline=a.host_pipeline, mask_folder=a.mask_folder, ignore_label=a.ignore_label,
+              tta=a.tta, confidence_folder=a.confidence_folder)
 
 
 if __name__ == "__main__":
