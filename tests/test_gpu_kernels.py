@@ -460,7 +460,8 @@ def test_dropout_mask_and_rng(hip):
     assert torch.equal(o1, o2)                                    # same (seed, index) -> same mask (backward regenerates it)
     x16 = x.to(torch.bfloat16); o16 = torch.empty_like(x16)       # bf16 tensors: the same mask, the kept values doubled exactly
     hip.unet_dropout(P(x16), c, P(o16), c, pix, c, None, 123, 0.5, 1, ST())
-    assert torch.equal(o16 != 0, (o1 != 0) & (x16 != 0)) or torch.equal((o16 != 0) | (x16 == 0), (o1 != 0) | (x16 == 0))
+    assert bool((x != 0).all()) and bool((x16 != 0).all())
+    assert torch.equal(o16 != 0, o1 != 0)                         # element for element (tests/test_gpu_misc_kernels.py pins the set itself)
     assert torch.equal(o16[o16 != 0].float(), (x16.float() * 2.0)[o16 != 0])
     keep = (o1 != 0).float().mean().item()
     assert abs(keep - 0.5) < 0.005
@@ -527,6 +528,7 @@ def test_keras_adam_flat(hip):
         ref_th, ref_m, ref_v = on.adam_keras_step(ref_th, g32, ref_m, ref_v, t, 3e-4, c)
     assert np.abs(thd.cpu().numpy() - ref_th).max() < 2e-6
     assert relerr(vd.cpu().numpy(), ref_v) < 1e-5
+    assert relerr(md.cpu().numpy(), ref_m) < 1e-5
 
 
 def test_winograd_weight_transform_batch_matches_single(hip):
