@@ -28,7 +28,10 @@ extern "C" {
 #define UNET_ENOSPC (-2)
 
 /* Bumped whenever an exported signature changes; a loader must refuse a library whose unet_hip_abi_version() differs
- * (9: + unet_convT2x2_dgrad_x6_sums (the BF16x6 transposed-conv data gradient leaves the producer layer's BatchNorm-backward sums); added under 9 without a
+ * (10: + unet_conv3x3_bf16_tile_channels, unet_convT2x2_bf16_tile_columns (host-only queries: which channel / column tile a bf16 launch takes, answered
+ *  by the launcher's own rule, so that a test can prove which kernel variant it ran); no existing signature changed;
+ *  9: + unet_convT2x2_dgrad_x6_sums, unet_convT2x2_x6_bnbwd_rows (the BF16x6 transposed-conv data gradient leaves the producer layer's BatchNorm-backward
+ *  sums, one row per 128-pixel tile); added under 9 without a
  *  bump, because no existing signature changed and a loader binds by name: unet_confusion_scores, unet_confusion_masks (per-class metrics);
  *  unet_softmax_ce_weighted(_workspace), unet_labels_onehot_ignore, unet_confusion_scores_valid (weighted loss, unlabeled pixels);
  *  unet_region_loss_workspace, unet_region_loss_sums, unet_region_loss_bwd (soft Dice / Tversky region term of the loss);
@@ -37,7 +40,7 @@ extern "C" {
  *  7: round 5 -- no signature changed, but the operand unet_winograd_weight_transform_x6 / _fold_x6 write is laid out for the round-5 kernel
  *  (MFMA A-operand order per 64-channel tile, chunk and point row): an operand and the conv entry point that reads it must come from one library;
  *  6: round 4 -- unet_convT2x2_*_x6; 5: round 4 -- the `_wg` (max_workgroups) entry points of every persistent kernel, unet_standin_collective; 4: round 4 -- the BF16x6 Winograd route: unet_*_x6; 3: + deferred bias gradient of unet_bn_bwd_any; 2: round 3 -- max_workgroups of the fused Winograd weight gradient; 1: rounds 1-2). */
-#define UNET_HIP_ABI_VERSION 9
+#define UNET_HIP_ABI_VERSION 10
 int unet_hip_abi_version(void);
 
 /* ---- Conv2D(3x3, 'same', relu) of UNet._conv_layer, UNet/model.py:28-35 (18 instances, :88-134) ------------------ */
@@ -134,6 +137,10 @@ int unet_conv3x3_bf16_pack_weights(const float* w, void* packed, int Cin, int Co
  *    for unet_bn_train_finalize_partials; data gradient, with r_prev = the saved activation of the layer whose dy is dx[..., c0:c1):
  *    (sum dx, sum dx * r_prev) for unet_bn_bwd_any / unet_bn_bwd_from_partials. */
 int unet_conv3x3_bf16_stats_rows(int N, int H, int W, int Cin, int Cout);
+/* output-channel tile the launch of unet_conv3x3_fwd_bf16 takes for this problem: 64 or 128; 0 if unsupported.  It depends on the device's
+ * compute-unit count (128 needs Cout % 128 == 0 and at least one workgroup per CU).  The data gradient of a Cin->Cout layer is asked as
+ * (N, H, W, Cout, Cin).  Host only, no side effect; the answer comes from the launcher's own rule. */
+int unet_conv3x3_bf16_tile_channels(int N, int H, int W, int Cin, int Cout);
 int unet_conv3x3_fwd_bf16(const void* x, int ldx, int x_bf16, const float* in_scale, const float* in_shift, const void* wp,
                           const float* bias, void* out, int ldo, int out_bf16,
                           int N, int H, int W, int Cin, int Cout, int relu, float* stat_part, size_t stat_bytes, void* stream);
@@ -240,6 +247,9 @@ int unet_convT2x2_bf16_supported(int N, int H, int W, int Cin, int Cout);
 size_t unet_convT2x2_bf16_packed_bytes(int Cin, int Cout);
 int unet_convT2x2_bf16_pack_weights(const float* w, void* packed, int Cin, int Cout, int mode, void* stream);
 int unet_convT2x2_bf16_stats_rows(int N, int H, int W, int Cin, int Cout, int dgrad);
+/* column tile of unet_convT2x2_fwd_bf16 (dgrad = 0) / unet_convT2x2_dgrad_bf16 (dgrad = 1) for this problem: 64 or 128; 0 if unsupported;
+ * in_bf16: the streamed operand (x / dz) is stored as bf16.  Host only, no side effect; the answer comes from the launcher's own rule. */
+int unet_convT2x2_bf16_tile_columns(int N, int H, int W, int Cin, int Cout, int dgrad, int in_bf16);
 int unet_convT2x2_fwd_bf16(const void* x, int ldx, int x_bf16, const void* wp, const float* bias, void* out, int ldo, int out_bf16,
                            int N, int H, int W, int Cin, int Cout, float* stat_part, size_t stat_bytes, void* stream);
 int unet_convT2x2_dgrad_bf16(const void* dz, int lddz, int dz_bf16, const void* wpd, void* dx, int lddx, int dx_bf16,

@@ -763,6 +763,21 @@ int conv_bf16_cus() {
 
 struct ConvBf16Stats { int mode; float* part; size_t bytes; const float* r; int ldr, c0, c1, r16; };
 
+#ifndef UNET_CB_NARROW_MAX
+#define UNET_CB_NARROW_MAX 0     /* diagnostic builds: 64-channel tiles (two workgroups per CU) for every layer with Cout <= this */
+#endif
+// The launch rule of run_conv_bf16, in two pieces that unet_conv3x3_bf16_tile_channels calls too (a query must not drift from the launch):
+// the pixel tiling, and whether the problem takes the 128-channel-tile kernels.
+// 128-channel tiles halve the input traffic; 64-channel tiles when they would leave compute units idle
+// (64-channel tiles for the K = 64 layers with 128 outputs -- two workgroups per CU hiding each other's epilogue -- were A/B-tested:
+// 64->128 @256^2 forward 0.111 -> 0.107 ms, 64->128 @512^2 data gradient + sums 0.401 -> 0.421 ms: no gain, wide tiles stay)
+void conv_bf16_pixel_tiles(ConvBf16Args& a, int N, int H, int W) {
+    a.tby = (H + 15) / 16; a.tbx = (W + 31) / 32; a.n_px = N * a.tby * a.tbx;
+}
+bool conv_bf16_wide(const ConvBf16Args& a, int Cout) {
+    return Cout % 128 == 0 && (long)a.n_px * (Cout / 128) >= conv_bf16_cus() && Cout > UNET_CB_NARROW_MAX;
+}
+
 int run_conv_bf16(const float* x, int ldx, const void* wp, const float* bias, float* out, int ldo,
                   int N, int H, int W, int Cin, int Cout, int relu, hipStream_t st, const ConvBf16Stats* stats = nullptr, int in16 = 0,
                   int out16 = 0, const float* in_scale = nullptr, const float* in_shift = nullptr, int max_workgroups = 0) {
@@ -771,15 +786,9 @@ int run_conv_bf16(const float* x, int ldx, const void* wp, const float* bias, fl
     a.in16 = in16; a.out16 = out16; a.r16 = stats ? stats->r16 : 0;
     a.x = x; a.wp = (const uint16_t*)wp; a.bias = bias; a.out = out; a.ldx = ldx; a.ldo = ldo;
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.relu = relu;
-    a.tby = (H + 15) / 16; a.tbx = (W + 31) / 32; a.n_px = N * a.tby * a.tbx;
+    conv_bf16_pixel_tiles(a, N, H, W);
     a.x_bytes = (unsigned)((size_t)N * H * W * ldx * (in16 ? 2 : 4));
-    // 128-channel tiles halve the input traffic; 64-channel tiles when they would leave compute units idle
-    // (64-channel tiles for the K = 64 layers with 128 outputs -- two workgroups per CU hiding each other's epilogue -- were A/B-tested:
-    // 64->128 @256^2 forward 0.111 -> 0.107 ms, 64->128 @512^2 data gradient + sums 0.401 -> 0.421 ms: no gain, wide tiles stay)
-#ifndef UNET_CB_NARROW_MAX
-#define UNET_CB_NARROW_MAX 0     /* diagnostic builds: 64-channel tiles (two workgroups per CU) for every layer with Cout <= this */
-#endif
-    const bool wide = Cout % 128 == 0 && (long)a.n_px * (Cout / 128) >= conv_bf16_cus() && Cout > UNET_CB_NARROW_MAX;
+    const bool wide = conv_bf16_wide(a, Cout);
     a.n_co = Cout / (wide ? 128 : 64);
     const int mode = stats ? stats->mode : 0;
     if (mode) {
@@ -831,6 +840,15 @@ extern "C" int unet_conv3x3_bf16_pack_weights(const float* w, void* packed, int 
 extern "C" int unet_conv3x3_bf16_stats_rows(int N, int H, int W, int Cin, int Cout) {
     if (!unet_conv3x3_bf16_supported(N, H, W, Cin, Cout)) return 0;
     return N * ((H + 15) / 16) * ((W + 31) / 32);
+}
+
+// output-channel tile the launch of unet_conv3x3_fwd_bf16 takes for this problem (64 or 128; 0: unsupported); the data gradient of a
+// Cin -> Cout layer is asked as (N, H, W, Cout, Cin), the arguments run_conv_bf16 receives from unet_conv3x3_dgrad_bf16.  Host only.
+extern "C" int unet_conv3x3_bf16_tile_channels(int N, int H, int W, int Cin, int Cout) {
+    if (!unet_conv3x3_bf16_supported(N, H, W, Cin, Cout)) return 0;
+    ConvBf16Args a{};
+    conv_bf16_pixel_tiles(a, N, H, W);
+    return conv_bf16_wide(a, Cout) ? 128 : 64;
 }
 
 // ---- weight gradient on the bf16 matrix cores ------------------------------------------------------------------------------
@@ -1672,6 +1690,22 @@ __global__ void convt_bf16_pack_kernel(const float* __restrict__ w, uint16_t* __
     reinterpret_cast<uint4*>(wp)[i] = make_uint4(v[0], v[1], v[2], v[3]);
 }
 
+// The launch rule of run_convt_bf16, in two pieces that unet_convT2x2_bf16_tile_columns calls too: the GEMM's shape and pixel tiling (mode 1
+// forward, 2 data gradient), and whether the problem takes the 128-column-tile kernels.
+// Forward with K <= 256 (up_1, up_2): 4-8 chunks of 32 MFMAs between a prologue whose first loads come from HBM and an epilogue that writes
+// 128 KB -- one workgroup per CU leaves every one of those latencies exposed.  64-column tiles at TWO workgroups per CU (128 accumulators,
+// 72 KB of LDS) hide them in each other; the input tile's extra reads come from L2 (column tile fastest).  Same box, forward + sums:
+// up_1 0.141 -> 0.112 ms, up_2 0.089 -> 0.079; at K >= 512 the wide tile wins (up_3 0.063 either way, up_4 0.050 vs 0.056), and the data
+// gradient's 64-column kernel with BatchNorm-backward sums does not fit 256 registers (it spills: 0.141 -> 0.161 on up_1).
+void convt_bf16_gemm_shape(ConvtBf16Args& a, int mode, int N, int H, int W, int Cin, int Cout) {
+    a.K = mode == 1 ? Cin : 4 * Cout; a.Ncol = mode == 1 ? 4 * Cout : Cin;
+    a.tby = (H + 15) / 16; a.tbx = (W + 31) / 32; a.n_px = N * a.tby * a.tbx;
+}
+bool convt_bf16_wide(const ConvtBf16Args& a, int mode, int in16) {
+    const bool narrow_k = UNET_CT_OCC > 1 && in16 && mode == 1 && a.K <= 256;
+    return a.Ncol % 128 == 0 && (long)a.n_px * (a.Ncol / 128) >= conv_bf16_cus() && !narrow_k;
+}
+
 int run_convt_bf16(int mode, const void* x, int ldx, int in16, const void* wp, const float* bias, float* out, int ldo,
                    int N, int H, int W, int Cin, int Cout, float* stat_part, size_t stat_bytes, const float* r_prev, int ldr, hipStream_t st,
                    int out16 = 0, int r16 = 0) {
@@ -1679,16 +1713,9 @@ int run_convt_bf16(int mode, const void* x, int ldx, int in16, const void* wp, c
     a.out16 = out16; a.r16 = r16;
     a.x = (const float*)x; a.wp = (const uint16_t*)wp; a.bias = bias; a.out = out; a.ldx = ldx; a.ldo = ldo;
     a.N = N; a.H = H; a.W = W; a.Cout = Cout; a.in16 = in16;
-    a.K = mode == 1 ? Cin : 4 * Cout; a.Ncol = mode == 1 ? 4 * Cout : Cin;
-    a.tby = (H + 15) / 16; a.tbx = (W + 31) / 32; a.n_px = N * a.tby * a.tbx;
+    convt_bf16_gemm_shape(a, mode, N, H, W, Cin, Cout);
     a.x_bytes = (unsigned)((size_t)N * H * W * (mode == 2 ? 4 : 1) * ldx * (in16 ? 2 : 4));
-    // Forward with K <= 256 (up_1, up_2): 4-8 chunks of 32 MFMAs between a prologue whose first loads come from HBM and an epilogue that writes
-    // 128 KB -- one workgroup per CU leaves every one of those latencies exposed.  64-column tiles at TWO workgroups per CU (128 accumulators,
-    // 72 KB of LDS) hide them in each other; the input tile's extra reads come from L2 (column tile fastest).  Same box, forward + sums:
-    // up_1 0.141 -> 0.112 ms, up_2 0.089 -> 0.079; at K >= 512 the wide tile wins (up_3 0.063 either way, up_4 0.050 vs 0.056), and the data
-    // gradient's 64-column kernel with BatchNorm-backward sums does not fit 256 registers (it spills: 0.141 -> 0.161 on up_1).
-    const bool narrow_k = UNET_CT_OCC > 1 && in16 && mode == 1 && a.K <= 256;
-    const bool wide = a.Ncol % 128 == 0 && (long)a.n_px * (a.Ncol / 128) >= conv_bf16_cus() && !narrow_k;
+    const bool wide = convt_bf16_wide(a, mode, in16);
     a.n_co = a.Ncol / (wide ? 128 : 64);
     a.stat_part = stat_part; a.bn_r = r_prev; a.bn_ldr = ldr;
     if (stat_part) {
@@ -1736,6 +1763,15 @@ extern "C" int unet_convT2x2_bf16_pack_weights(const float* w, void* packed, int
 extern "C" int unet_convT2x2_bf16_stats_rows(int N, int H, int W, int Cin, int Cout, int dgrad) {
     if (!unet_convT2x2_bf16_supported(N, H, W, Cin, Cout)) return 0;
     return (dgrad ? 1 : 4) * N * ((H + 15) / 16) * ((W + 31) / 32);
+}
+// column tile (64 or 128; 0: unsupported) the launch of unet_convT2x2_fwd_bf16 (dgrad = 0) / unet_convT2x2_dgrad_bf16 (dgrad = 1) takes
+// for this problem; in_bf16: the streamed operand (x / dz) is stored as bf16.  Host only.
+extern "C" int unet_convT2x2_bf16_tile_columns(int N, int H, int W, int Cin, int Cout, int dgrad, int in_bf16) {
+    if (!unet_convT2x2_bf16_supported(N, H, W, Cin, Cout)) return 0;
+    const int mode = dgrad ? 2 : 1;
+    ConvtBf16Args a{};
+    convt_bf16_gemm_shape(a, mode, N, H, W, Cin, Cout);
+    return convt_bf16_wide(a, mode, in_bf16 ? 1 : 0) ? 128 : 64;
 }
 // z[n,2i+a,2j+b,co] = bias[co] + sum_ci x[n,i,j,ci] W[a,b,co,ci] (operands rounded to bf16, fp32 accumulation); H, W: input size;
 // x_bf16 / out_bf16: x / the output stored as bf16 (leading dimensions in elements; ldo even); stat_part nullable: BatchNorm sums of
