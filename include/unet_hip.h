@@ -36,6 +36,7 @@ extern "C" {
  *  unet_softmax_ce_weighted(_workspace), unet_labels_onehot_ignore, unet_confusion_scores_valid (weighted loss, unlabeled pixels);
  *  unet_region_loss_workspace, unet_region_loss_sums, unet_region_loss_bwd (soft Dice / Tversky region term of the loss);
  *  unet_image_tile_gather_tta, unet_prob_accumulate, unet_argmax_paste_conf (test-time augmentation and confidence maps of the inference pipeline);
+ *  unet_border_weights_workspace, unet_border_weights (border-distance loss weights: an exact Euclidean distance transform of each batch's masks);
  *  8: round 6 -- + unet_bn_finalize_apply_any (statistics finalize merged into the apply launch); the bf16 3x3 kernels start their accumulators at the bias;
  *  7: round 5 -- no signature changed, but the operand unet_winograd_weight_transform_x6 / _fold_x6 write is laid out for the round-5 kernel
  *  (MFMA A-operand order per 64-channel tile, chunk and point row): an operand and the conv entry point that reads it must come from one library;
@@ -386,6 +387,31 @@ int unet_region_loss_sums(const float* prob, int ldp, const int* labels_onehot, 
                           void* stream);
 int unet_region_loss_bwd(const float* prob, int ldp, const int* labels_onehot, int ignore_empty, const float* coef, float* dlogits, int lddz,
                          int N, long HW, int K, void* stream);
+/* Border-distance pixel weights for that loss, from the step's own labels (csrc/border_weights.hip): the single-transform "distance to the class
+ * border" form of the U-Net recipe's weight map.  Per image -- nothing crosses the image index n:
+ *       c(p)  = truth class of pixel p = first maximum of its one-hot row (the loop of unet_softmax_ce_weighted); a row with no positive entry
+ *               is UNLABELED
+ *       B     = the labeled pixels with a labeled 4-neighbour INSIDE the image whose class differs: both sides of a class border are in B, the
+ *               image edge is no border, an unlabeled pixel is never in B and puts no neighbour in it
+ *       d2(p) = the exact squared Euclidean distance in pixels from p to the nearest pixel of B, int32; 0 on B; UNET_BORDER_NONE when the
+ *               image has no border pixel at all
+ *       w(p)  = (1 + w0 * exp(d2(p) * neg_inv_2sigma2)) * m(p), evaluated in double from the fp32 arguments and rounded to fp32 once: the
+ *               stored weight is the fp32 rounding of the exact value (a step with this map is then, bit for bit, the step with that map
+ *               handed in as pixel_weight; an fp32 expf would differ in the last bit, which Adam's g / (|g| + eps) magnifies where g is
+ *               near zero);  the term is exactly 0 where d2 == UNET_BORDER_NONE;
+ *               m = pixel_weight_in[p] (fp32 [N][H][W]), or 1 when that pointer is NULL
+ * neg_inv_2sigma2 = (float)(-1 / (2 sigma^2)), formed by the caller in double and rounded once.  weights_out fp32 [N][H][W]; d2_out int32
+ * [N][H][W] (may be NULL).  Integer arithmetic until the final exponential, no atomics, no floating-point sums: d2 is exact and every output has the
+ * same bits run after run.  Nothing but the two outputs and ws is written.
+ * UNET_EINVAL (nothing launched): H or W > 16384 (H^2 + W^2 must stay below 2^31; a row of W int32 is the row pass's LDS, 64 KiB at the limit: no
+ * narrower W limit), N, H, W or K < 1, K > 255 (one class byte per pixel), w0 negative or not finite, neg_inv_2sigma2 not finite or not < 0, a NULL
+ * labels_onehot / weights_out / ws, ws not 4-byte aligned.  UNET_ENOSPC: ws_bytes < unet_border_weights_workspace(N, H, W) (0 for a refused shape). */
+#define UNET_BORDER_NONE 2147483647
+size_t unet_border_weights_workspace(int N, int H, int W);
+int unet_border_weights(const int* labels_onehot, int K, const float* pixel_weight_in /* may be NULL */,
+                        float w0, float neg_inv_2sigma2, float* weights_out /* [N,H,W] */,
+                        int* d2_out /* [N,H,W], may be NULL */, int N, int H, int W,
+                        void* ws, size_t ws_bytes, void* stream);
 /* np.argmax(softmax, axis=-1), UNet/inference.py:107,166 (first maximum wins) */
 int unet_argmax(const float* p, int ldp, int* out, long P, int K, void* stream);
 

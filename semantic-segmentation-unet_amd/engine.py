@@ -24,6 +24,7 @@ from ._lib import lib
 from .plan import BF16, EngineOptions, PRODUCER, build_plan, layer_table      # noqa: F401  (layer_table / PRODUCER re-exported)
 
 BASE = 64                      # UNet._BASELINE_FEATURE_DEPTH  (reference UNet/model.py:20)
+UNET_BORDER_NONE = 2 ** 31 - 1 # include/unet_hip.h: the squared border distance of an image without a class border
 SIZE_FACTOR = 16               # UNet.SIZE_FACTOR              (reference UNet/model.py:25)
 
 # Keras defaults the reference relies on (SURVEY.md 8(a) "(K)"): one place to flip them.
@@ -945,3 +946,29 @@ class Engine:
         out = self._buf("argmax", (n, h, w), torch.int32)
         self.L.unet_argmax(_p(prob), k, _p(out), n * h * w, k, self._stream())
         return out
+
+    def border_weights(self, labels, w0, sigma, pixel_weights=None, return_d2=False):
+        """Border-distance loss weights of a batch's own labels (unet_border_weights; include/unet_hip.h has the definition):
+        w = (1 + w0 * exp(-d2 / (2 sigma^2))) * pixel_weights, d2 the exact squared distance to the nearest class-border pixel of the same
+        image.  labels int32 one-hot [N,H,W,K] (an all-zero row is unlabeled), pixel_weights fp32 [N,H,W] or None, both contiguous on the
+        device.  -> fp32 [N,H,W], with return_d2 also int32 [N,H,W] (UNET_BORDER_NONE where the image has no border): the engine's own
+        buffers, kept per shape like every other, valid until the next call.  Four launches on the current stream, no host sync."""
+        if not (torch.is_tensor(labels) and labels.device == self.theta.device and labels.dtype == torch.int32 and labels.dim() == 4 and labels.is_contiguous()):
+            raise ValueError("labels must be a contiguous int32 one-hot tensor [N,H,W,K] on %s" % self.dev)
+        n, h, w, k = labels.shape
+        w0, sigma = float(w0), float(sigma)
+        if not (math.isfinite(w0) and w0 >= 0 and math.isfinite(sigma) and sigma > 0):
+            raise ValueError("border weight must be finite and >= 0, sigma finite and > 0")
+        pw = pixel_weights
+        if pw is not None and not (torch.is_tensor(pw) and pw.device == self.theta.device and pw.dtype == torch.float32
+                                   and tuple(pw.shape) == (n, h, w) and pw.is_contiguous()):
+            raise ValueError("pixel_weights must be a contiguous fp32 tensor %s on %s" % ([n, h, w], self.dev))
+        nb = self.L.unet_border_weights_workspace(n, h, w)
+        ws = self._buf("border_ws", (int(nb) + 256,), torch.uint8)
+        out = self._buf("border_w", (n, h, w))
+        d2 = self._buf("border_d2", (n, h, w), torch.int32) if return_d2 else None
+        c = float(np.float32(-1.0 / (2.0 * sigma * sigma)))            # formed in double, rounded once
+        self._timed("border_weights", self._nb(labels, out, pw, d2), self.L.unet_border_weights,
+                    _p(labels), k, _p(pw), w0, c, _p(out), _p(d2), n, h, w, _p(ws), nb, self._stream())
+        self._border_keepalive = (labels, pw)
+        return (out, d2) if return_d2 else out

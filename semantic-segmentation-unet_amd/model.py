@@ -101,6 +101,19 @@ def check_region(dice_weight, tversky, dice_smooth, dice_class_weights, number_c
     return None if lam == 0 else (lam, alpha, beta, smooth, cw)
 
 
+def check_border(border_weight, border_sigma):
+    """The border-distance weight's settings, validated on the host: -> None when border_weight == 0, else (w0, sigma)"""
+    try:
+        w0, sigma = float(border_weight), float(border_sigma)
+    except (TypeError, ValueError):
+        raise ValueError("border_weight and border_sigma must be numbers")
+    if not np.isfinite(w0) or w0 < 0:
+        raise ValueError("border_weight must be finite and >= 0")
+    if not np.isfinite(sigma) or sigma <= 0:
+        raise ValueError("border_sigma must be finite and > 0")
+    return None if w0 == 0 else (w0, sigma)
+
+
 class _KerasLikeModel:
     """`unet.get_keras_model()`: callable as m(x, training=False) with x fp32 [N,C,H,W] (numpy or torch), returning the
     softmax [N,H,W,K] (reference UNet/inference.py:105,164; UNet/model.py:177,209,239)."""
@@ -142,8 +155,13 @@ class UNet:
 
     def __init__(self, number_classes, global_batch_size, number_channels, learning_rate=3e-4, label_smoothing=0,
                  device="cuda", seed=0, compute_dtype=None, class_weights=None, ignore_unlabeled=False,
-                 dice_weight=0.0, tversky=(0.5, 0.5), dice_smooth=1.0, dice_class_weights=None):
-        """dice_weight (lambda >= 0), tversky = (alpha, beta) >= 0, dice_smooth (s > 0), dice_class_weights (length number_classes, >= 0, not
+                 dice_weight=0.0, tversky=(0.5, 0.5), dice_smooth=1.0, dice_class_weights=None, border_weight=0.0, border_sigma=5.0):
+        """border_weight (w0 >= 0), border_sigma (sigma > 0, pixels): every step forms the U-Net recipe's border weight map from its own labels
+        on the device, w(p) = 1 + w0 exp(-d(p)^2 / (2 sigma^2)) with d the exact Euclidean distance from p to the nearest pixel that has a
+        4-neighbour of another class in the same image (unet_border_weights), and hands it on as the step's pixel_weights, multiplied into the
+        caller's where given.  Per image: no new collective, independent of how a batch is split.  Like pixel_weights it does not enter the
+        region term.  border_weight = 0: the launches of before.
+        dice_weight (lambda >= 0), tversky = (alpha, beta) >= 0, dice_smooth (s > 0), dice_class_weights (length number_classes, >= 0, not
         all zero; normalised to sum 1): the compound loss CE + lambda / G * sum over the local images n and the classes k of c~_k (1 - T_nk),
         T_nk = (I + s) / ((1 - alpha - beta) I + alpha S + beta Y + s) the soft Tversky index of image n (alpha = beta = 0.5: soft Dice) over
         its labeled pixels; class_weights and pixel_weights do not enter it.  Per image and divided by the global batch size, like the
@@ -158,6 +176,7 @@ class UNet:
         self.global_batch_size = global_batch_size
         self.label_smoothing = label_smoothing
         region = check_region(dice_weight, tversky, dice_smooth, dice_class_weights, number_classes)     # before anything touches the device
+        self.border = check_border(border_weight, border_sigma)  # None, or (w0, sigma)
         self.engine = Engine(number_classes, number_channels, device=device, seed=seed)
         self.ignore_unlabeled = bool(ignore_unlabeled)
         self.class_weights = None
@@ -255,12 +274,28 @@ class UNet:
             return pixel_weights.to(device=self.engine.dev, dtype=torch.float32).contiguous()
         return torch.as_tensor(check_weights(pixel_weights, "pixel_weights", (n, h, w))).to(self.engine.dev)
 
-    def _loss_kw(self, pixel_weights, images):
+    def border_weight_map(self, labels, pixel_weights=None, return_distance=False):
+        """The border weight map of a batch of one-hot labels [N,H,W,K] (numpy or tensor), as the steps form it: fp32 [N,H,W] on the device,
+        the caller's pixel_weights multiplied in; with return_distance also the int32 squared distances (engine.UNET_BORDER_NONE where an
+        image has no class border).  Needs border_weight > 0.  The tensors are the caller's own (copies of the engine's buffers)."""
+        if self.border is None:
+            raise ValueError("border_weight_map needs a network built with border_weight > 0")
+        lab = (labels if torch.is_tensor(labels) else torch.as_tensor(np.asarray(labels, dtype=np.int32))).to(self.engine.dev).contiguous()
+        if lab.dim() != 4 or lab.dtype != torch.int32:
+            raise ValueError("labels must be int32 one-hot [N,H,W,K]")
+        pw = self._pixel_weights(pixel_weights, lab.permute(0, 3, 1, 2))
+        out = self.engine.border_weights(lab, self.border[0], self.border[1], pixel_weights=pw, return_d2=return_distance)
+        return (out[0].clone(), out[1].clone()) if return_distance else out.clone()
+
+    def _loss_kw(self, pixel_weights, images, labels=None):
         """forward()'s weighted-loss keywords; empty when nothing is set, so the default step calls forward() as it always did"""
         kw = {}
         if self.class_weights is not None:
             kw["class_weights"] = self.class_weights
-        if pixel_weights is not None:
+        if self.border is not None and labels is not None:       # the step's own labels -> the map, the caller's weights multiplied in
+            kw["pixel_weights"] = self.engine.border_weights(labels.to(self.engine.dev).contiguous(), self.border[0], self.border[1],
+                                                             pixel_weights=self._pixel_weights(pixel_weights, images))
+        elif pixel_weights is not None:
             kw["pixel_weights"] = self._pixel_weights(pixel_weights, images)
         if self.ignore_unlabeled:
             kw["ignore_unlabeled"] = True
@@ -275,9 +310,11 @@ class UNet:
         e = self.engine
         images = torch.as_tensor(np.asarray(images, dtype=np.float32)) if not torch.is_tensor(images) else images
         labels = torch.as_tensor(np.asarray(labels, dtype=np.int32)) if not torch.is_tensor(labels) else labels
+        if self.border is not None:
+            labels = labels.to(e.dev).contiguous()               # one upload serves the map and the loss
         e.forward(images, training=True, dropout_masks=dropout_masks, labels=labels,
                   global_batch_size=self.global_batch_size, label_smoothing=self.label_smoothing, want_grad=True, confusion=confusion,
-                  **self._loss_kw(pixel_weights, images))
+                  **self._loss_kw(pixel_weights, images, labels))
         if self.parallel is not None:
             self.parallel.begin_step()
         e.backward()
@@ -292,8 +329,10 @@ class UNet:
         e = self.engine
         images = torch.as_tensor(np.asarray(images, dtype=np.float32)) if not torch.is_tensor(images) else images
         labels = torch.as_tensor(np.asarray(labels, dtype=np.int32)) if not torch.is_tensor(labels) else labels
+        if self.border is not None:
+            labels = labels.to(e.dev).contiguous()               # one upload serves the map and the loss
         e.forward(images, training=False, labels=labels, global_batch_size=self.global_batch_size,
-                  label_smoothing=self.label_smoothing, confusion=confusion, **self._loss_kw(pixel_weights, images))
+                  label_smoothing=self.label_smoothing, confusion=confusion, **self._loss_kw(pixel_weights, images, labels))
         return self._update_metrics(images, loss_metric, accuracy_metric)
 
     def _update_metrics(self, images, loss_metric, accuracy_metric):

@@ -82,10 +82,20 @@ def region_settings(dice_weight=0.0, tversky_alpha=0.5, tversky_beta=0.5, dice_s
     return kw
 
 
+def border_settings(border_weight=0.0, border_sigma=5.0):
+    """`--border_weight W0`, `--border_sigma S` -> the keywords of model.UNet for the border-distance weight map ({} when the weight is 0: the
+    network is then built as before); ValueError names the option at fault."""
+    try:
+        b = unet_model_module.check_border(border_weight, border_sigma)
+    except ValueError as e:
+        raise ValueError(str(e).replace("border_", "--border_"))
+    return {} if b is None else {"border_weight": b[0], "border_sigma": b[1]}
+
+
 def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, test_lmdb_filepath, use_augmentation,
                 number_classes, balance_classes, learning_rate, test_every_n_steps, early_stopping_count,
                 train_reader=None, test_reader=None, max_epochs=None, quiet=False, compute_dtype=None, unet_factory=None,
-                class_metrics=False, class_weights=None, ignore_label=None, region=None):
+                class_metrics=False, class_weights=None, ignore_label=None, region=None, border=None):
     """unet_factory (tests): callable(number_classes, global_batch_size, number_channels, learning_rate, device=..., compute_dtype=...)
     standing in for model.UNet, so the loop semantics can be checked without a GPU; the default is the HIP-backed class, which
     refuses to run anywhere but on an MI355X.
@@ -101,7 +111,11 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
 
     region (opt-in extra; region_settings()'s dict): the soft Dice / Tversky term of the loss (model.UNet(dice_weight=, tversky=, dice_smooth=,
     dice_class_weights=)).  Train and test steps then return CE + region, so test_loss.csv, the best checkpoint and early stopping follow
-    the compound loss; with class_metrics the test epoch's line also carries the mean soft index per class."""
+    the compound loss; with class_metrics the test epoch's line also carries the mean soft index per class.
+
+    border (opt-in extra; border_settings()'s dict): the border-distance weight map (model.UNet(border_weight=, border_sigma=)), formed on the
+    device from every train and test step's own labels -- behind the device augmentation, so it follows the warped masks; unlabeled pixels
+    (ignore_label) are no border.  Combines with class_weights, ignore_label and region."""
     say = (lambda *a: None) if quiet else print
     # the weighted-loss options are checked before anything is opened
     if class_weights is not None:
@@ -111,6 +125,8 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
         if unet_model_module.check_region(region.get("dice_weight", 0.0), region.get("tversky", (0.5, 0.5)), region.get("dice_smooth", 1.0),
                                           region.get("dice_class_weights"), number_classes) is None:
             region = None
+    if border:
+        border = border_settings(**border)
     if ignore_label is not None:
         ignore_label = int(ignore_label)
         if not 0 <= ignore_label <= 255:
@@ -205,6 +221,8 @@ def train_model(output_folder, batch_size, reader_count, train_lmdb_filepath, te
             loss_kw["ignore_unlabeled"] = True
         if region:
             loss_kw.update(region)
+        if border:
+            loss_kw.update(border)
         net = (unet_factory or unet_model_module.UNet)(number_classes, global_batch_size, number_channels, learning_rate,
                                                        device=dev_, compute_dtype=compute_dtype, **loss_kw)
         strategy = None
@@ -369,7 +387,15 @@ def main(argv=None):
     ap.add_argument("--dice_smooth", dest="dice_smooth", type=float, default=1.0, help="smoothing constant s > 0 of the index")
     ap.add_argument("--dice_class_weights", dest="dice_class_weights", type=str, default=None,
                     help="w0,w1,...: weight of each class's index in the term (finite, >= 0, not all zero; normalised to sum 1)")
+    ap.add_argument("--border_weight", dest="border_weight", type=float, default=0.0,
+                    help="w0 >= 0: every pixel's loss is multiplied by 1 + w0 exp(-d^2 / (2 sigma^2)), d = its distance in pixels to the nearest "
+                         "class border of its mask, computed on the device from each batch's (augmented) masks; 0 = off")
+    ap.add_argument("--border_sigma", dest="border_sigma", type=float, default=5.0, help="sigma > 0 of --border_weight, in pixels")
     a = ap.parse_args(argv)
+    try:
+        border = border_settings(a.border_weight, a.border_sigma)
+    except ValueError as e:
+        ap.error(str(e))
     try:
         region = region_settings(a.dice_weight, a.tversky_alpha, a.tversky_beta, a.dice_smooth, a.dice_class_weights, a.number_classes)
     except ValueError as e:
@@ -395,7 +421,8 @@ def main(argv=None):
     train_model(a.output_folder, a.batch_size, a.reader_count, a.train_database_filepath, a.test_database_filepath,
                 a.use_augmentation, a.number_classes, a.balance_classes, a.learning_rate, a.test_every_n_steps,
                 a.early_stopping_count, train_reader=tr, test_reader=te, max_epochs=a.max_epochs, compute_dtype=a.compute_dtype,
-                class_metrics=a.class_metrics, class_weights=class_weights, ignore_label=a.ignore_label, region=region or None)
+                class_metrics=a.class_metrics, class_weights=class_weights, ignore_label=a.ignore_label, region=region or None,
+                border=border or None)
 
 
 if __name__ == "__main__":
