@@ -37,6 +37,7 @@ extern "C" {
  *  unet_region_loss_workspace, unet_region_loss_sums, unet_region_loss_bwd (soft Dice / Tversky region term of the loss);
  *  unet_image_tile_gather_tta, unet_prob_accumulate, unet_argmax_paste_conf (test-time augmentation and confidence maps of the inference pipeline);
  *  unet_border_weights_workspace, unet_border_weights (border-distance loss weights: an exact Euclidean distance transform of each batch's masks);
+ *  unet_label_components_workspace, unet_label_components (instance labels: connected components of a batch of class maps, added under 10 the same way);
  *  8: round 6 -- + unet_bn_finalize_apply_any (statistics finalize merged into the apply launch); the bf16 3x3 kernels start their accumulators at the bias;
  *  7: round 5 -- no signature changed, but the operand unet_winograd_weight_transform_x6 / _fold_x6 write is laid out for the round-5 kernel
  *  (MFMA A-operand order per 64-channel tile, chunk and point row): an operand and the conv entry point that reads it must come from one library;
@@ -412,6 +413,32 @@ int unet_border_weights(const int* labels_onehot, int K, const float* pixel_weig
                         float w0, float neg_inv_2sigma2, float* weights_out /* [N,H,W] */,
                         int* d2_out /* [N,H,W], may be NULL */, int N, int H, int W,
                         void* ws, size_t ws_bytes, void* stream);
+/* Instance labels: connected components of a batch of class maps (csrc/components.hip).  Per image -- nothing crosses the image index n:
+ *   connected   two pixels that are 4- or 8-neighbours (`connectivity`), carry the same class, and that class is not `background` (-1: no class is
+ *               background).  Components never span images or classes.
+ *   labels_out  int32 [N,H,W]: 0 on background, else 1 + the rank of the component among its image's components, ordered by the row-major index
+ *               of each component's first pixel.  count_out[n] = components of image n.  A function of the mask alone, the same bits run after run.
+ *   min_area    A > 0 (needs a background class): components of fewer than A pixels are removed -- 0 in labels_out, `background` in mask_out; the
+ *               survivors keep their order and are renumbered 1..count.  Nothing merges: background is not labelled.
+ *   mask_out    may be NULL; the filtered class map, same element size, dense [N,H,W]; may be `mask` itself when mask_pitch == W
+ *   objects_out may be NULL; int64 [N, max_objects, 8], row i - 1 for label i: class, area, y0, x0, y1, x1 (inclusive box), sum of y, sum of x.
+ *               All integers: exact and order-independent (centroid = sum / area on the host).  count_out reports the true number also beyond
+ *               max_objects and labels_out is complete; only rows < min(count, max_objects) are written, the rest is not touched.
+ * mask: uint8 (mask_elem 1) or int32 (4) [N,H,W], mask_pitch elements between rows, H * mask_pitch between images; it is only read (unless aliased).
+ * Union-find with the smaller linear index as parent: per 32 x 64 tile in LDS, then across tile borders with agent-scope atomic loads and atomicMin,
+ * then flattened; a per-root area; a three-launch exclusive scan over the kept roots in row-major order (roots are first pixels: the canonical
+ * numbering); relabel + table.  No loop waits for another workgroup; the only atomics are minimum-index links and integer add / min / max.
+ * ws: 16-byte aligned, unet_label_components_workspace(N, H, W) bytes (0 for a refused shape).  Nothing but the outputs and ws is written.
+ * UNET_EINVAL (nothing launched): connectivity not 4 / 8, mask_elem not 1 / 4, N, H or W < 1, N*H*W >= 2^31, mask_pitch < W, background < -1 (or
+ * > 255 with uint8), min_area < 0, min_area > 0 without a background, objects_out with max_objects < 1, a NULL mask / labels_out / count_out / ws,
+ * a misaligned pointer, an output or ws overlapping the input or another output (other than mask_out == mask with dense rows).
+ * UNET_ENOSPC: ws_bytes too small. */
+size_t unet_label_components_workspace(int N, int H, int W);
+int unet_label_components(const void* mask, int mask_elem /* 1 | 4 */, long mask_pitch /* elements per row */,
+                          int N, int H, int W, int connectivity, int background /* -1: none */, int min_area,
+                          int* labels_out /* [N,H,W] */, int* count_out /* [N] */,
+                          void* mask_out /* may be NULL */, long long* objects_out /* may be NULL */, int max_objects,
+                          void* ws, size_t ws_bytes, void* stream);
 /* np.argmax(softmax, axis=-1), UNet/inference.py:107,166 (first maximum wins) */
 int unet_argmax(const float* p, int ldp, int* out, long P, int K, void* stream);
 

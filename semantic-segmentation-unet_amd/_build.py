@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libunet_hip.so")
 SOURCES = ["conv_igemm.hip", "conv_wgrad.hip", "conv_direct.hip", "winograd.hip", "winograd_x6.hip", "convt_stream.hip", "convt_x6.hip", "conv_bf16.hip", "augment.hip",
-           "norm.hip", "misc.hip", "loss.hip", "region_loss.hip", "border_weights.hip", "inference.hip", "inference_tta.hip", "metrics.hip", "crc32c.hip"]
+           "norm.hip", "misc.hip", "loss.hip", "region_loss.hip", "border_weights.hip", "components.hip", "inference.hip", "inference_tta.hip", "metrics.hip", "crc32c.hip"]
 HEADERS = ["common.h", "wino_epilogue.h", "ends_inline.h"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-source additions.  winograd_x6.hip: the split steps in the MFMA gaps are scalar fp32 subtractions on purpose -- SLP vectorisation turns the

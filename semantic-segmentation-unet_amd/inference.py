@@ -24,6 +24,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
+from . import components
 from . import model as unet_model_module
 from ._lib import lib
 from .readers import zscore_normalize
@@ -156,6 +157,14 @@ def _host_confusion(mask, truth, confusion, ignore_label=-1):
 
 TTA_CHOICES = (1, 2, 4, 8)
 SegmentResult = collections.namedtuple("SegmentResult", ["mask", "confidence", "probabilities"])
+InstanceResult = collections.namedtuple("InstanceResult", ["mask", "confidence", "probabilities", "labels", "count", "objects"])
+
+
+def _check_instances(instances, connectivity, background, min_object_area, max_objects):
+    """-> None when no instance stage is asked for, else (connectivity, background or -1, min_area, max_objects), checked"""
+    if not instances and not min_object_area:
+        return None
+    return (connectivity,) + components._check_options(connectivity, background, min_object_area, max_objects)
 
 
 def _check_tta(tta):
@@ -226,11 +235,13 @@ def _segment_tta_host(img, unet, tile_size, tta=1):
 
 
 def _segment_host_pipeline(raw, unet, tile_size=TILE_SIZE, truth=None, confusion=None, ignore_label=-1, tta=1, return_confidence=False,
-                           return_probabilities=False):
+                           return_probabilities=False, instances=False, connectivity=8, background=0, min_object_area=0, max_objects=65536):
     """the reference's loop (UNet/inference.py:201-213): float32, z-score over the whole image, whole-image or tiled driver.  With
     truth / confusion the mask is scored on the host (the counts `segment_image` takes on the device).  tta / return_confidence /
-    return_probabilities: as `segment_image`, through `_segment_tta_host`."""
+    return_probabilities: as `segment_image`, through `_segment_tta_host`.  instances / min_object_area: as `segment_image`, through
+    `components.label_components_host`, before the scoring."""
     tta = _check_tta(tta)
+    inst = _check_instances(instances, connectivity, background, min_object_area, max_objects)
     if truth is not None or confusion is not None:
         truth = _check_truth(truth, confusion, raw.shape[0], raw.shape[1])
     img = raw.astype(np.float32)
@@ -243,15 +254,19 @@ def _segment_host_pipeline(raw, unet, tile_size=TILE_SIZE, truth=None, confusion
         mask = _inference_tiling(img, unet, tile_size)
     else:
         mask = _inference(img, unet)
+    if inst is not None:
+        labels, count, objects, mask = components.label_components_host(mask, *inst)
     if confusion is not None:
         _host_confusion(mask, truth, confusion, ignore_label)
+    if inst is not None:
+        return InstanceResult(mask, conf if return_confidence else None, probs if return_probabilities else None, labels, count, objects)
     if return_confidence or return_probabilities:
         return SegmentResult(mask, conf if return_confidence else None, probs if return_probabilities else None)
     return mask
 
 
 def segment_image(img, unet, tile_size=TILE_SIZE, radius=None, truth=None, confusion=None, ignore_label=-1, tta=1, return_confidence=False,
-                  return_probabilities=False):
+                  return_probabilities=False, instances=False, connectivity=8, background=0, min_object_area=0, max_objects=65536):
     """Raw image (HW or HWC, any dtype `_read` returns) -> class map [H, W], the mask `_inference` / `_inference_tiling` compute on the
     z-scored image, bit for bit, with the whole pipeline on the device: one upload of the image in its raw dtype (uint8 / uint16 / fp32;
     anything else is converted to fp32 on the host first, as the host path does), then per entry of `tile_plan` gather (reflect padding,
@@ -277,8 +292,17 @@ def segment_image(img, unet, tile_size=TILE_SIZE, radius=None, truth=None, confu
     `SegmentResult(mask, confidence, probabilities)` -- fp32 [H, W] probability of the winning class, fp32 [H, W, K] mean softmax, None for
     what was not asked -- written by `unet_argmax_paste_conf` (with tta = 1 straight from the softmax, no accumulate), each downloaded once
     behind the same single synchronise.  `_segment_tta_host` states the arithmetic; both agree bit for bit.  With tta = 1 and nothing
-    asked for, the launches and the returned array are exactly those described above."""
+    asked for, the launches and the returned array are exactly those described above.
+
+    instances=True, or min_object_area > 0: ONE `unet_label_components` call (components.label_components) follows the last paste on the same
+    stream, before the scoring: connected components of the class map (`connectivity` 4 or 8; pixels of class `background` -- None: no such
+    class -- belong to no object), objects of fewer than min_object_area pixels turned into background, numbered by first pixel.  The return
+    value becomes `InstanceResult(mask, confidence, probabilities, labels, count, objects)`: mask the FILTERED class map (what truth /
+    confusion then score), labels int32 [H, W] (0 = background), count the number of objects, objects int64 [max_objects, 8] (class, area,
+    y0, x0, y1, x1, sum y, sum x; `components.objects_table` turns it into centroids), each one more non-blocking download behind the single
+    synchronise.  `components.label_components_host` states it on the host; both agree exactly.  With neither option set nothing changes."""
     tta = _check_tta(tta)
+    inst = _check_instances(instances, connectivity, background, min_object_area, max_objects)
     img = np.asarray(img)
     if img.ndim not in (2, 3):
         raise IOError("Invalid number of dimensions for input image. Expecting HW or HWC dimension ordering.")
@@ -294,7 +318,8 @@ def segment_image(img, unet, tile_size=TILE_SIZE, radius=None, truth=None, confu
     hp, wp = h + (-h) % SIZE_FACTOR, w + (-w) % SIZE_FACTOR
     if h == 1 or w == 1:                             # padded to 16: unet_image_tile_gather refuses it (UNET_EINVAL)
         return _segment_host_pipeline(img, unet, tile_size, truth=truth, confusion=confusion, ignore_label=ignore_label, tta=tta,
-                                      return_confidence=return_confidence, return_probabilities=return_probabilities)
+                                      return_confidence=return_confidence, return_probabilities=return_probabilities, instances=instances,
+                                      connectivity=connectivity, background=background, min_object_area=min_object_area, max_objects=max_objects)
     e, L = unet.engine, lib()
     dev = e.dev
     if scoring and (confusion.device != torch.empty(0, device=dev).device or confusion.number_classes != unet.number_classes):
@@ -351,6 +376,18 @@ def segment_image(img, unet, tile_size=TILE_SIZE, radius=None, truth=None, confu
                                      None if conf is None else ptr(conf), w, None if probs is None else ptr(probs), st)
         else:
             L.unet_argmax_paste(ptr(src), k, th, tw, k, zy - ty, zx - tx, zh, zw, ptr(mask), mask.element_size(), w, zy, zx, h, w, st)
+    if inst is not None:
+        if inst[1] > 255 and mdt == torch.uint8:
+            raise ValueError("the class map has no class %d to use as background" % inst[1])
+        comp = components.label_components(mask, inst[0], inst[1], inst[2], inst[3], want_objects=True, want_mask=inst[2] > 0, stream=st, library=L)
+        if comp.mask is not None:
+            mask = comp.mask
+        labels_out = torch.empty((h, w), dtype=torch.int32, pin_memory=True)
+        labels_out.copy_(comp.labels, non_blocking=True)
+        count_out = torch.empty((), dtype=torch.int32, pin_memory=True)
+        count_out.copy_(comp.count, non_blocking=True)
+        objects_out = torch.empty((inst[3], 8), dtype=torch.int64, pin_memory=True)
+        objects_out.copy_(comp.objects, non_blocking=True)
     if scoring:
         confusion.update_from_masks(mask, truth_dev, ignore_label, st)
     out = torch.empty((h, w), dtype=mdt, pin_memory=True)
@@ -365,6 +402,9 @@ def segment_image(img, unet, tile_size=TILE_SIZE, radius=None, truth=None, confu
     del raw_host, coef_host                          # (pinned sources of the uploads: alive until the synchronise above)
     if scoring:
         del truth_host
+    if inst is not None:
+        return InstanceResult(out.numpy(), conf_out.numpy() if conf is not None else None, probs_out.numpy() if probs is not None else None,
+                              labels_out.numpy(), int(count_out.numpy()), objects_out.numpy())
     if extra:
         return SegmentResult(out.numpy(), conf_out.numpy() if conf is not None else None, probs_out.numpy() if probs is not None else None)
     return out.numpy()
@@ -455,7 +495,8 @@ def mask_dtype(max_label):
 
 
 def inference(checkpoint_filepath, image_folder, output_folder, number_classes, number_channels, image_format, compute_dtype=None,
-              host_pipeline=False, mask_folder=None, ignore_label=-1, tta=1, confidence_folder=None):
+              host_pipeline=False, mask_folder=None, ignore_label=-1, tta=1, confidence_folder=None, instance_folder=None, connectivity=8,
+              background_class=0, min_object_area=0, max_objects=65536):
     """host_pipeline: the reference's host loop per tile (`_inference` / `_inference_tiling`) instead of `segment_image`; the masks are
     the same.  The file of image i is written by one worker thread while image i + 1 is segmented: files appear in order, every write
     has finished when this returns, and the first exception of a write is raised here.
@@ -467,8 +508,24 @@ def inference(checkpoint_filepath, image_folder, output_folder, number_classes, 
 
     tta (opt-in extra): test-time augmentation, see `segment_image`; the masks written (and scored) are those of the averaged softmax.
     confidence_folder (opt-in extra): receives one fp32 [H, W] file per image with the image's name, the probability of the winning
-    class, written by the same worker thread right after the mask (.npy, or a TIFF like the mask's when the format is a TIFF)."""
+    class, written by the same worker thread right after the mask (.npy, or a TIFF like the mask's when the format is a TIFF).
+
+    instance_folder (opt-in extra): receives one label map per image with the image's name (0 = background, objects numbered from 1 by
+    first pixel; uint16 when the image has fewer than 65536 objects, else int32; .npy or a TIFF by the format), and the output folder
+    `objects.csv` (one row per object: image, label, class, area, y0, x0, y1, x1, centroid_y, centroid_x; at most max_objects per image)
+    and `object_counts.csv` (image, objects).  connectivity / background_class (-1: none) / min_object_area / max_objects: see
+    `segment_image`.  min_object_area alone writes the filtered masks and none of the instance files."""
     tta = _check_tta(tta)
+    inst_kw = {}
+    if instance_folder is not None or min_object_area:
+        background = None if background_class is None or background_class < 0 else background_class
+        _check_instances(True, connectivity, background, min_object_area, max_objects)
+        inst_kw = dict(instances=True, connectivity=connectivity, background=background, min_object_area=min_object_area, max_objects=max_objects)
+    if instance_folder is not None:
+        if image_format != "npy" and "tif" not in image_format:
+            raise ValueError("--instance_folder writes uint16 / int32 files: --image_format must be npy or a TIFF, not %s" % image_format)
+        os.makedirs(instance_folder, exist_ok=True)
+    object_rows, count_rows = [], []
     if confidence_folder is not None:
         if image_format != "npy" and "tif" not in image_format:
             raise ValueError("--confidence_folder writes float32 files: --image_format must be npy or a TIFF, not %s" % image_format)
@@ -497,9 +554,18 @@ def inference(checkpoint_filepath, image_folder, output_folder, number_classes, 
                 kw = dict(truth=_read(os.path.join(mask_folder, name)), confusion=per_image, ignore_label=ignore_label)
             if tta != 1 or confidence_folder is not None:
                 kw.update(tta=tta, return_confidence=confidence_folder is not None)
+            kw.update(inst_kw)
             seg = _segment_host_pipeline(raw, unet, **kw) if host_pipeline else segment_image(raw, unet, **kw)
-            conf = None
-            if confidence_folder is not None:
+            conf = labels = None
+            if inst_kw:
+                if instance_folder is not None:
+                    labels = seg.labels.astype(np.uint16 if seg.count < 65536 else np.int32)
+                    count_rows.append("%s,%d" % (name, seg.count))
+                    for r in components.objects_table(seg.count, seg.objects):
+                        object_rows.append("%s,%d,%d,%d,%d,%d,%d,%d,%r,%r" % ((name, r["label"], r["class"], r["area"]) + tuple(r["bbox"])
+                                                                               + (float(r["centroid_y"]), float(r["centroid_x"]))))
+                seg, conf = seg.mask, seg.confidence
+            elif confidence_folder is not None:
                 seg, conf = seg.mask, seg.confidence
             if mask_folder is not None:
                 counts = per_image.result()
@@ -511,6 +577,8 @@ def inference(checkpoint_filepath, image_folder, output_folder, number_classes, 
             writes.append(writer.submit(_write, os.path.join(output_folder, name), seg, image_format))
             if conf is not None:                      # the same single worker: behind the mask of this image, before the next one's
                 writes.append(writer.submit(_write, os.path.join(confidence_folder, name), conf, image_format))
+            if labels is not None:
+                writes.append(writer.submit(_write, os.path.join(instance_folder, name), labels, image_format))
     finally:
         writer.shutdown(wait=True)                    # drain: every submitted write has run (or failed) before this returns
     for f in writes:
@@ -520,6 +588,13 @@ def inference(checkpoint_filepath, image_folder, output_folder, number_classes, 
             f.write(metrics.csv_header("image", number_classes) + "\n")
             f.writelines(r + "\n" for r in score_rows + [metrics.csv_row("total", metrics.summarize(total))])
         np.save(os.path.join(output_folder, "confusion.npy"), total)
+    if instance_folder is not None:
+        with open(os.path.join(output_folder, "objects.csv"), "w") as f:
+            f.write("image,label,class,area,y0,x0,y1,x1,centroid_y,centroid_x\n")
+            f.writelines(r + "\n" for r in object_rows)
+        with open(os.path.join(output_folder, "object_counts.csv"), "w") as f:
+            f.write("image,objects\n")
+            f.writelines(r + "\n" for r in count_rows)
 
 
 def main(argv=None):
@@ -545,10 +620,20 @@ def main(argv=None):
     ap.add_argument("--confidence_folder", dest="confidence_folder", type=str, default=None,
                     help="opt-in extra: also write the probability of the winning class per pixel, one float32 file per image with the "
                          "image's name (.npy or TIFF by --image_format)")
+    ap.add_argument("--instance_folder", dest="instance_folder", type=str, default=None,
+                    help="opt-in extra: also write an instance label map per image (connected components of the mask, 0 = background) with the "
+                         "image's name, and objects.csv / object_counts.csv into the output folder")
+    ap.add_argument("--connectivity", dest="connectivity", type=int, choices=[4, 8], default=8, help="with the instance options: 4- or 8-neighbours")
+    ap.add_argument("--background_class", dest="background_class", type=int, default=0,
+                    help="with the instance options: the class whose pixels belong to no object (-1: every class forms objects)")
+    ap.add_argument("--min_object_area", dest="min_object_area", type=int, default=0,
+                    help="opt-in extra: objects of fewer pixels are turned into background in the written masks (alone: no instance files)")
+    ap.add_argument("--max_objects", dest="max_objects", type=int, default=65536, help="with --instance_folder: rows of objects.csv per image at most")
     a = ap.parse_args(argv)
     inference(a.checkpoint_filepath, a.image_folder, a.output_folder, a.number_classes, a.number_channels, a.image_format,
               compute_dtype=a.compute_dtype, host_pipeline=a.host_pipeline, mask_folder=a.mask_folder, ignore_label=a.ignore_label,
-              tta=a.tta, confidence_folder=a.confidence_folder)
+              tta=a.tta, confidence_folder=a.confidence_folder, instance_folder=a.instance_folder, connectivity=a.connectivity,
+              background_class=a.background_class, min_object_area=a.min_object_area, max_objects=a.max_objects)
 
 
 if __name__ == "__main__":
